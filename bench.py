@@ -12,7 +12,11 @@ One step = one pass of the hot path over one batch of HBM-resident synthetic u8 
 Weak scaling: every rank embeds 256 faces; the gallery is row-sharded across ranks.
 value = faces embedded by all ranks / max-over-ranks wall time of the timed steps.
 
-Launch: python bench.py --gpus N --steps K --warmup W
+Launch: python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
+  A plain run sets up, warms up, times the K steps, writes the last step's outputs if --dump-outputs is given
+  and prints the result line.  --full adds what takes runs of its own: the per-kernel event timing and roofline
+  (the timed steps then replay graphs with one timed launch each), the rocprofv3 --pmc traffic passes, the
+  N = 1 run at config 4's 1M-row gallery and the CPU baseline.
   N > 1 either under torch.distributed.run (RANK/WORLD_SIZE set), or directly: the parent process then
   never touches the GPU and starts N fresh child processes, one per GPU, with RANK/LOCAL_RANK/
   WORLD_SIZE/MASTER_ADDR=127.0.0.1/MASTER_PORT set (launch_ranks).
@@ -70,8 +74,8 @@ def pmc_passes(args):
     from pmc_traffic import per_kernel
     if not shutil.which("rocprofv3"):
         return None, "rocprofv3 not on PATH"
-    child = [sys.executable, os.path.abspath(__file__), "--steps", "2", "--warmup", "1", "--no-cpu-baseline",
-             "--no-prof", "--no-pmc", "--no-n1-1m", "--arch", args.arch, "--batch", str(args.batch), "--k", str(args.k)]
+    child = [sys.executable, os.path.abspath(__file__), "--steps", "2", "--warmup", "1",  # a plain run
+             "--arch", args.arch, "--batch", str(args.batch), "--k", str(args.k)]
     if args.dtype:
         child += ["--dtype", args.dtype]
     if args.gallery_rows:
@@ -123,9 +127,19 @@ def parse():
     ap.add_argument("--arch", default="iresnet100")
     ap.add_argument("--dtype", default=None,
                     help="bf16 | f16 | fp8 (default: the arch's parity dtype; fp8 = BASELINE config 5)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything beside the headline: per-kernel event timing and roofline, the "
+                         "live rocprofv3 --pmc traffic passes, the N = 1 run at the 1M-row gallery and the CPU "
+                         "baseline (each can be switched off with its --no-* option); a plain run times the "
+                         "steps and prints the result line, nothing else")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last step returned as DIR/<name>.npy: "
+                         "embeddings (f32 [B, 512]), topk_scores (f32 [B, k]), topk_indices (f64 [B, k], global "
+                         "gallery rows); inputs, weights and gallery are seeded, so two builds compare output "
+                         "for output")
     ap.add_argument("--cpu-seconds", type=float, default=12.0, help="bound on the CPU-baseline sample")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-prof", action="store_true", help="skip the per-kernel event timing (roofline)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
+    ap.add_argument("--no-prof", action="store_true", help="--full: skip the per-kernel event timing (roofline)")
     ap.add_argument("--eager-prof", action="store_true",
                     help="time every 8th launch of the dominant class in eager steps instead of graph slots")
     ap.add_argument("--no-pmc", action="store_true",
@@ -139,7 +153,18 @@ def parse():
     ap.add_argument("--host-input", action="store_true",
                     help="crops start in pinned host memory and are copied H2D inside each step "
                          "(PCIe-inclusive rate, DESIGN.md; never the headline value)")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if not args.full:  # a plain run: the headline only
+        args.no_cpu_baseline = args.no_prof = args.no_pmc = args.no_n1_1m = True
+    return args
+
+
+def dump_outputs(path, emb, scores, indices):
+    """--dump-outputs: the last timed step's results as float .npy files (indices are exact in f64)."""
+    os.makedirs(path, exist_ok=True)
+    np.save(os.path.join(path, "embeddings.npy"), emb.detach().cpu().numpy().astype(np.float32))
+    np.save(os.path.join(path, "topk_scores.npy"), scores.detach().cpu().numpy().astype(np.float32))
+    np.save(os.path.join(path, "topk_indices.npy"), indices.detach().cpu().numpy().astype(np.float64))
 
 
 def _time_embed(model, arch, u8, M):
@@ -391,6 +416,8 @@ def main():
     # libraries, tools/variant.sh, whose results are wrong by construction)
     if os.environ.get("FR_TIMING_ONLY") != "1":
         assert int(out_i[:, 0].min()) >= 0 and int(out_i[:, 0].max()) < rows
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, emb if world == 1 else matcher.all_emb, out_s, out_i)  # every rank's probes
 
     faces = world * B * args.steps
     value = faces / elapsed

@@ -8,7 +8,7 @@ for r in $(seq 1 $N); do
   for v in $V; do
     tag=$(echo "$v" | tr "=,;/." "_____")
     if [ "$v" = base ]; then env_set=""; else env_set="${v//;/ }"; fi  # several VAR=value: separated by ;
-    env $env_set timeout -k 10 200 python bench.py --no-cpu-baseline --no-pmc --no-n1-1m --steps 20 --warmup 5 $AB_ARGS > $O/${tag}_$r.log 2>&1 || { echo "$v failed"; tail -20 $O/${tag}_$r.log; exit 1; }
+    env $env_set timeout -k 10 200 python bench.py --full --no-cpu-baseline --no-pmc --no-n1-1m --steps 20 --warmup 5 $AB_ARGS > $O/${tag}_$r.log 2>&1 || { echo "$v failed"; tail -20 $O/${tag}_$r.log; exit 1; }
     python - $O/${tag}_$r.log "$v" <<'PY'
 import json, sys
 d = json.loads(open(sys.argv[1]).read().strip().splitlines()[-1])

@@ -7,7 +7,7 @@ grep -E "passed|failed|rel|1-cos" $O/tests.log | tail -20
 i=0
 for ab in "${ABS[@]}"; do
   i=$((i+1))
-  FR_AB=$ab timeout -k 10 300 python bench.py --arch resnet50_arcface --no-cpu-baseline --no-pmc --steps 30 > "$O/bench_${i}_$ab.log" 2>&1 || { tail -20 "$O/bench_${i}_$ab.log"; exit 1; }
+  FR_AB=$ab timeout -k 10 300 python bench.py --full --arch resnet50_arcface --no-cpu-baseline --no-pmc --steps 30 > "$O/bench_${i}_$ab.log" 2>&1 || { tail -20 "$O/bench_${i}_$ab.log"; exit 1; }
   grep '^{' "$O/bench_${i}_$ab.log" | python -c "
 import json,sys
 d=json.loads(sys.stdin.read()); print('AB=$ab value', d['value'], 'ms/step', d['ms_per_step'])

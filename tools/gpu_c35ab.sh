@@ -7,7 +7,7 @@ grep -E "passed|failed|rel" $O/tests.log | tail -8
 for r in 1 2; do
 for v in base $1; do
   if [ $v = base ]; then L=""; else L="FR_LIBFRHIP=facerecognition_amd/lib/variants/libfrhip_$v.so"; fi
-  env $L timeout -k 10 200 python bench.py --arch irv1_facenet --no-cpu-baseline --no-pmc --no-n1-1m --steps 20 --warmup 5 > $O/${v}_$r.log 2>&1 || { tail -20 $O/${v}_$r.log; exit 1; }
+  env $L timeout -k 10 200 python bench.py --full --arch irv1_facenet --no-cpu-baseline --no-pmc --no-n1-1m --steps 20 --warmup 5 > $O/${v}_$r.log 2>&1 || { tail -20 $O/${v}_$r.log; exit 1; }
   grep '^{' $O/${v}_$r.log | python -c "
 import json,sys
 d=json.loads(sys.stdin.read()); k=d['kernels']

@@ -5,7 +5,7 @@ ABS=("$@"); [ ${#ABS[@]} -eq 0 ] && ABS=("" "no_chain")
 timeout -k 10 400 python -u -m pytest tests/test_gpu_chain.py -x -v -s -p no:cacheprovider --timeout 300 --timeout-method thread > $O/tests.log 2>&1 || { tail -40 $O/tests.log; exit 1; }
 grep -E "passed|failed|rel|1-cos" $O/tests.log | tail -20
 for ab in "${ABS[@]}"; do
-  FR_AB=$ab timeout -k 10 300 python bench.py --arch irv1_facenet --no-cpu-baseline --no-pmc --steps 30 > "$O/bench_$ab.log" 2>&1 || { tail -20 "$O/bench_$ab.log"; exit 1; }
+  FR_AB=$ab timeout -k 10 300 python bench.py --full --arch irv1_facenet --no-cpu-baseline --no-pmc --steps 30 > "$O/bench_$ab.log" 2>&1 || { tail -20 "$O/bench_$ab.log"; exit 1; }
   grep '^{' "$O/bench_$ab.log" | python -c "
 import json,sys
 d=json.loads(sys.stdin.read()); print('AB=$ab value', d['value'], 'ms/step', d['ms_per_step'])

@@ -13,7 +13,7 @@ elif [ "$K" != none ]; then
   step tests 600 python -u -m pytest tests -m gpu -x -q -s -p no:cacheprovider --timeout 120 --timeout-method thread -k "$K"
   grep -E "passed|failed" $O/tests.log | tail -2
 fi
-step bench 400 python bench.py "$@"
+step bench 400 python bench.py --full "$@"
 grep '^{' $O/bench.log | tail -1 > $O/bench.json
 python tools/show_bench.py $O/bench.json
 echo "[$(date +%T)] done"

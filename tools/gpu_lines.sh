@@ -13,7 +13,7 @@ elif [ "$K" != none ]; then
   step tests 600 python -u -m pytest tests -m gpu -x -q -s -p no:cacheprovider --timeout 120 --timeout-method thread -k "$K"
   grep -E "passed|failed" $O/tests.log | tail -1
 fi
-B="python bench.py --no-cpu-baseline --no-pmc --no-n1-1m"
+B="python bench.py --full --no-cpu-baseline --no-pmc --no-n1-1m"
 step bench 300 $B
 step bench_bs1 300 $B --batch 1 --steps 50 --warmup 10 --no-prof
 step bench_irv1 300 $B --arch irv1_facenet

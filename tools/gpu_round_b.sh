@@ -4,11 +4,11 @@
 set -o pipefail
 T=${1:?tag}; R=$(pwd); O=$R/gpurun_out/$T; mkdir -p $O
 step() { local name=$1 lim=$2; shift 2; echo "[$(date +%T)] $name"; timeout -k 10 $lim "$@" > $O/$name.log 2>&1; local rc=$?; if [ $rc -ne 0 ]; then echo "$name failed rc=$rc"; tail -20 $O/$name.log; exit $rc; fi; }
-BCMD="$R/bench.py --steps 10 --warmup 3 --no-cpu-baseline"
+BCMD="$R/bench.py --full --steps 10 --warmup 3 --no-cpu-baseline"
 cd /tmp && export TMPDIR=/tmp
 step rocprof 400 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof -o run -- python $BCMD
-step pmc_fetch 400 rocprofv3 --pmc FETCH_SIZE --output-format csv -d $O/pf -o run -- python $R/bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-prof
-step pmc_write 400 rocprofv3 --pmc WRITE_SIZE --output-format csv -d $O/pw -o run -- python $R/bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-prof
+step pmc_fetch 400 rocprofv3 --pmc FETCH_SIZE --output-format csv -d $O/pf -o run -- python $R/bench.py --full --steps 3 --warmup 1 --no-cpu-baseline --no-prof
+step pmc_write 400 rocprofv3 --pmc WRITE_SIZE --output-format csv -d $O/pw -o run -- python $R/bench.py --full --steps 3 --warmup 1 --no-cpu-baseline --no-prof
 cd $R
 python tools/pmc_traffic.py --fetch $O/pf --write $O/pw --out $O/pmc_traffic.json
 find $O/prof -name "*kernel_stats.csv" | head -1 | xargs -r head -8

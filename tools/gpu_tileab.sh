@@ -7,7 +7,7 @@ tail -n 1 $O/tests.log
 for arch in irv1_facenet irv1_facenet resnet50_arcface iresnet100; do
   for v in base $V; do
     if [ $v = base ]; then L=""; else L="FR_LIBFRHIP=facerecognition_amd/lib/variants/libfrhip_$v.so"; fi
-    env $L timeout -k 10 300 python bench.py --arch $arch --no-cpu-baseline --no-pmc --steps 30 > $O/bench_${arch}_$v.log 2>&1 || { tail -20 $O/bench_${arch}_$v.log; exit 1; }
+    env $L timeout -k 10 300 python bench.py --full --arch $arch --no-cpu-baseline --no-pmc --steps 30 > $O/bench_${arch}_$v.log 2>&1 || { tail -20 $O/bench_${arch}_$v.log; exit 1; }
     grep '^{' $O/bench_${arch}_$v.log | python -c "
 import json,sys
 d=json.loads(sys.stdin.read()); print('$arch $v', d['value'], d['ms_per_step'])

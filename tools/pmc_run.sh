@@ -13,7 +13,7 @@ P2=${PMC_P2:-"SQ_INSTS_LDS,SQ_INSTS_VALU,SQ_INSTS_SALU,SQ_INSTS_VMEM,SQ_LDS_IDX_
 i=1
 for P in $P1 $P2; do
   echo "[$(date +%T)] pass $i: $P"
-  timeout -s KILL 120 rocprofv3 --pmc ${P//,/ } --output-format csv -d $O/p$i -o run -- python $R/bench.py $ARGS > $O/p$i.log 2>&1
+  timeout -s KILL 120 rocprofv3 --pmc ${P//,/ } --output-format csv -d $O/p$i -o run -- python $R/bench.py --full $ARGS > $O/p$i.log 2>&1
   rc=$?
   if [ $rc -ne 0 ]; then echo "pass $i failed rc=$rc"; tail -5 $O/p$i.log; exit $rc; fi
   i=$((i+1))
