@@ -17,4 +17,11 @@ def __getattr__(name):  # lazy: importing the package must not initialise the GP
     if name == "DeviceGallery":
         from .gallery import DeviceGallery
         return DeviceGallery
+    if name in _EVALUATE:
+        from . import evaluate
+        return getattr(evaluate, name)
     raise AttributeError(name)
+
+
+_EVALUATE = ("compute_metrics", "threshold_sweep", "roc_analysis", "generate_report", "evaluate_recognition_engine",
+             "closed_set_report", "evaluate_closed_set")

@@ -80,6 +80,9 @@ _SIGS = {
     "fr_gallery_rows": (c_int64, [c_void_p]),
     "fr_gallery_write": (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_int, c_int]),
     "fr_match_topk": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p]),
+    "fr_match_eval": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
+                              c_void_p, c_int, ctypes.c_float, ctypes.c_float, c_void_p]),
+    "fr_debug_match_eval_splits": (c_int, [c_void_p, c_int]),
     "fr_topk_merge": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]),
     "fr_topk_merge_ranks": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]),
     "fr_embed_match": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p,

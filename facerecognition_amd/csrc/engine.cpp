@@ -3074,6 +3074,46 @@ int fr_match_topk(fr_handle* h, const float* P, int B, int k, float* scores, int
     return match_locked(h, P, B, k, scores, idx, stream);
 }
 
+int fr_match_eval(fr_handle* h, const float* P, int B, const int32_t* true_idx, int k, float* scores, int32_t* idx,
+                  float* true_score, int32_t* true_rank, uint64_t* hist, int nbins, float lo, float hi, void* stream) {
+    const bool want_topk = k != 0;  // k = 0: scores / idx are not written (and may be NULL)
+    if (!P || !true_idx || !true_score || !true_rank || B <= 0) {
+        set_error("fr_match_eval: bad argument (P, true_idx, true_score, true_rank must be set, B >= 1)");
+        return FR_ERR_ARG;
+    }
+    if (want_topk && (k <= 0 || !scores || !idx)) {
+        set_error("fr_match_eval: bad argument (k >= 1 with scores and idx, or k = 0 for no top-k)");
+        return FR_ERR_ARG;
+    }
+    if (hist && (nbins < 1 || nbins > 2048 || !(hi > lo))) {
+        set_error("fr_match_eval: bad argument (1 <= nbins <= 2048 and hi > lo with a histogram)");
+        return FR_ERR_ARG;
+    }
+    if (!h) { set_error("fr_match_eval: null handle"); return FR_ERR_ARG; }
+    std::lock_guard<std::mutex> lk(h->mu);
+    if (!h->gallery || h->g_rows <= 0) { set_error("fr_match_eval: no gallery"); return FR_ERR_STATE; }
+    if (h->g_rows > 0x7fffffff) { set_error("fr_match_eval: needs a gallery below 2^31 rows"); return FR_ERR_ARG; }
+    if (want_topk) {  // fr_match_topk's launches, unchanged
+        int rc = match_locked(h, P, B, k, scores, idx, stream);
+        if (rc) return rc;
+    }
+    FR_HIP_CHECK(hipSetDevice(h->device));
+    const float inv_w = hist ? (float)nbins / (hi - lo) : 0.f;  // rounded once, here
+    FR_HIP_CHECK(launch_match_eval(P, B, h->gallery, h->g_rows, h->g_dim, h->g_base, true_idx, true_score, true_rank,
+                                   (unsigned long long*)hist, nbins, lo, inv_w, (hipStream_t)stream));
+    return FR_OK;
+}
+
+int fr_debug_match_eval_splits(fr_handle* h, int B) {
+    if (!h || B <= 0) { set_error("fr_debug_match_eval_splits: bad argument"); return FR_ERR_ARG; }
+    std::lock_guard<std::mutex> lk(h->mu);
+    if (!h->gallery || h->g_rows <= 0) { set_error("fr_debug_match_eval_splits: no gallery"); return FR_ERR_STATE; }
+    int n_split;
+    int64_t rps;
+    match_eval_plan(B, h->g_rows, h->g_dim, &n_split, &rps);
+    return n_split;
+}
+
 int fr_topk_merge(const float* cand_s, const int32_t* cand_i, int B, int n_lists, int k, float* scores,
                   int32_t* idx, void* stream) {
     if (!cand_s || !cand_i || !scores || !idx || B <= 0 || n_lists <= 0 || k <= 0 || k > 16) {

@@ -326,6 +326,13 @@ hipError_t launch_match_x3(const float* P, int B, const float* G, const bf16_t* 
 // Choose n_split / rows_per_split for a (B, N) match.
 void match_split_plan(int B, int64_t N, int* n_split, int64_t* rows_per_split);
 void match_split_plan(int B, int64_t N, int D, int k, int* n_split, int64_t* rows_per_split);  // exact path
+// Labelled evaluation (match_eval.hip): per probe the exact score of its true row (global index true_idx, -inf /
+// rank -1 when outside [index_base, index_base + N)), the number of rows that sort before it, and optionally the
+// impostor-score histogram hist [nbins] (u64, added to; bin = clamp(floor((s - lo) * inv_w), 0, nbins - 1)).
+void match_eval_plan(int B, int64_t N, int D, int* n_split, int64_t* rows_per_split);
+hipError_t launch_match_eval(const float* P, int B, const float* G, int64_t N, int D, int64_t index_base,
+                             const int32_t* true_idx, float* true_score, int32_t* true_rank,
+                             unsigned long long* hist, int nbins, float lo, float inv_w, hipStream_t s);
 hipError_t launch_segment_mean_normalize(const float* E, int D, const int32_t* seg_start, int n_seg,
                                          float* out, hipStream_t s);
 // Gallery preparation: rows with |‖g‖-1| >= 1e-3 divided by ‖g‖ (cosine_similarity semantics).

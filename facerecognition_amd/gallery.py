@@ -119,6 +119,71 @@ class DeviceGallery:
         s, i = self.search_device(p, k)
         return s.cpu().numpy(), i.cpu().numpy().astype(np.int64)
 
+    def evaluate_device(self, probes_dev, true_idx_dev, k: int = 5, hist_bins: int = 0,
+                        hist_range: Tuple[float, float] = (-1.0, 1.0), hist=None):
+        """Labelled evaluation on the device (fr_match_eval): probes_dev cuda f32 [B, D], true_idx_dev cuda
+        int32 [B] (each probe's true gallery row, a global index as ``search`` returns them).  Returns a
+        dict of device tensors: ``scores`` / ``idx`` [B, k] exactly as ``search_device`` (None with k = 0),
+        ``true_score`` [B] f32, ``true_rank`` [B] int32 (0-based position of the true row in the match
+        order; -1 and -inf for a row outside this shard) and ``hist`` [hist_bins] int64, the counts of all
+        impostor scores over ``hist_range`` (None with hist_bins = 0).  Pass the ``hist`` of an earlier
+        call to accumulate over probe chunks."""
+        import torch
+
+        p = probes_dev.float().contiguous()
+        B = int(p.shape[0])
+        t = true_idx_dev.to(device=self.device, dtype=torch.int32).contiguous()
+        if tuple(t.shape) != (B,):
+            raise ValueError(f"evaluate_device: true_idx must be [{B}]")
+        s = torch.empty((B, k), dtype=torch.float32, device=self.device) if k else None
+        i = torch.empty((B, k), dtype=torch.int32, device=self.device) if k else None
+        ts = torch.empty((B,), dtype=torch.float32, device=self.device)
+        tr = torch.empty((B,), dtype=torch.int32, device=self.device)
+        if hist_bins and hist is None:
+            hist = torch.zeros((hist_bins,), dtype=torch.int64, device=self.device)
+        if hist is not None and (hist.dtype != torch.int64 or tuple(hist.shape) != (hist_bins,)
+                                 or not hist.is_contiguous() or not hist.is_cuda):
+            raise ValueError(f"evaluate_device: hist must be a contiguous cuda int64 [{hist_bins}]")
+        N.check(N.lib().fr_match_eval(self._h, N.ptr(p), B, N.ptr(t), k, N.ptr(s), N.ptr(i), N.ptr(ts), N.ptr(tr),
+                                      N.ptr(hist), hist_bins, float(hist_range[0]), float(hist_range[1]),
+                                      N.stream_ptr(self.device)), "fr_match_eval")
+        return {"scores": s, "idx": i, "true_score": ts, "true_rank": tr, "hist": hist}
+
+    def evaluate(self, probes, true_idx, k: int = 5, hist_bins: int = 0,
+                 hist_range: Tuple[float, float] = (-1.0, 1.0), chunk: int = 8192) -> dict:
+        """``evaluate_device`` with numpy in and out (idx / true_rank / hist as int64).  Probes go to the
+        device ``chunk`` rows at a time; the histogram accumulates over the chunks."""
+        import torch
+
+        p = torch.as_tensor(np.asarray(probes, dtype=np.float32) if not torch.is_tensor(probes) else probes)
+        p = p.reshape(-1, self.d)
+        t = torch.as_tensor(np.asarray(true_idx).astype(np.int32) if not torch.is_tensor(true_idx) else true_idx)
+        t = t.reshape(-1)
+        B = int(p.shape[0])
+        if int(t.shape[0]) != B:
+            raise ValueError("evaluate: one true_idx per probe")
+        if self.ntotal == 0:
+            raise RuntimeError("evaluate: empty gallery")
+        parts = []
+        hist = None
+        for b0 in range(0, B, chunk):
+            r = self.evaluate_device(p[b0:b0 + chunk].to(self.device), t[b0:b0 + chunk].to(self.device), k,
+                                     hist_bins, hist_range, hist)
+            hist = r["hist"]
+            parts.append(r)
+
+        if not parts:
+            raise ValueError("evaluate: no probes")
+
+        def cat(key, dtype):
+            if parts[0][key] is None:
+                return None
+            return torch.cat([q[key] for q in parts]).cpu().numpy().astype(dtype)
+
+        return {"scores": cat("scores", np.float32), "idx": cat("idx", np.int64),
+                "true_score": cat("true_score", np.float32), "true_rank": cat("true_rank", np.int64),
+                "hist": None if hist is None else hist.cpu().numpy()}
+
     def close(self) -> None:
         if self._own and getattr(self, "_h", None):
             N.lib().fr_destroy(self._h)

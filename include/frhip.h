@@ -130,6 +130,28 @@ int fr_gallery_write(fr_handle* h, const float* G, int64_t row0, int64_t n, int 
  * so a large-k list starts with the small-k list.  k > 16 needs N < 2^31. */
 int fr_match_topk(fr_handle* h, const float* P, int B, int k, float* scores, int32_t* idx, void* stream);
 
+/* Labelled evaluation of P [B, D] (device f32) against the gallery, without the B x N score matrix
+ * (replaces the host similarity matrix of evaluate_arcface_kaggle.ipynb cells 15-19 -- argmax,
+ * argsort[:, -5:], sims[i, true_idx], max(axis=1) -- and the per-image loop of
+ * inference/evaluate.py:275-349).  true_idx [B] int32 (device) is each probe's true gallery row as a
+ * global index, in the index space of fr_match_topk's idx (index_base included).  Results (device):
+ *   scores / idx [B, k]  exactly fr_match_topk's (the same launches); k = 0 skips them (both may be
+ *                        NULL then, and neither is written);
+ *   true_score [B] f32   the score of row true_idx[b], the bits the exact f32 match path gives that pair;
+ *   true_rank [B] int32  the number of gallery rows sorting before the true row in fr_match_topk's order
+ *                        (score descending, index ascending): its 0-based position, so
+ *                        true_rank[b] < k <=> idx[b, true_rank[b]] == true_idx[b];
+ *   hist [nbins] u64     (NULL: none) the scores of all pairs (b, j) with j != true_idx[b], ADDED to the
+ *                        caller's (zeroed) counts, so that probe chunks accumulate;
+ *                        bin = clamp((int)floorf((s - lo) * inv_w), 0, nbins - 1) with inv_w =
+ *                        (float)nbins / (hi - lo), every operation rounded to f32 on its own;
+ *                        1 <= nbins <= 2048, hi > lo.
+ * A true_idx outside [index_base, index_base + N) (another shard's row, or negative) gives true_score
+ * -inf and true_rank -1, and all N rows count as impostors of that probe.  N < 2^31. */
+int fr_match_eval(fr_handle* h, const float* P, int B, const int32_t* true_idx, int k,
+                  float* scores, int32_t* idx, float* true_score, int32_t* true_rank,
+                  uint64_t* hist, int nbins, float lo, float hi, void* stream);
+
 /* Merge n_lists candidate lists per probe: cand_s/cand_i [B, n_lists, k] → [B, k]
  * with the same (score desc, index asc) order.  Used after the RCCL all-gather of
  * per-shard candidates. */
@@ -343,6 +365,8 @@ int fr_get_option(const fr_handle* h, int option);
 /* Number of probes (since the gallery was first split) whose bf16x3 candidate proof failed and were
  * rescanned exactly (synchronizes the device). */
 int fr_debug_match_fallbacks(fr_handle* h);
+/* Number of gallery splits fr_match_eval's main pass takes for a batch of B probes (no device work). */
+int fr_debug_match_eval_splits(fr_handle* h, int B);
 /* Number of bounded waits of the split stage kernels (layer2: two workgroups per image, layer1: four,
  * exchanging boundary rows per conv) that ran out before the partner published; 0 on a healthy device
  * (synchronizes the device).  Each one was either re-run (fr_embed's default) or reported as
