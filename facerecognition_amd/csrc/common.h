@@ -17,6 +17,10 @@ void set_error(const std::string& msg);
 // A/B switches from the FR_AB environment variable (engine.cpp): "key" or "key=value", comma separated
 const char* ab_str(const char* key);
 int ab_int(const char* key, int dflt);
+// Opts `kernel` in to `bytes` of dynamic LDS on the current device (engine.cpp): hipFuncSetAttribute runs once per
+// (kernel, device) and again only for a larger size; safe under concurrent first launches.  Not a stream operation,
+// and after the first eager launch no HIP call that touches the device at all.
+hipError_t lds_opt_in(const void* kernel, int bytes);
 
 #define FR_HIP_CHECK(expr)                                                        \
     do {                                                                          \

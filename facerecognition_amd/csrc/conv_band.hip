@@ -649,11 +649,7 @@ static hipError_t launch_bandp_k(const ConvArgs& a, hipStream_t s) {
     constexpr int LDS = 2 * 8 * P64 * 16 + WS * BN * 128;
     static_assert(LDS <= 160 * 1024, "band LDS budget");
     auto k = conv3x3_bandp_kernel<F16, W, TH, WM, WN, FM, FN, WS>;
-    static bool attr = false;
-    if (!attr) {
-        (void)hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
-        attr = true;
-    }
+    if (hipError_t e = lds_opt_in((const void*)k, LDS); e != hipSuccess) return e;
     const int ntn = (a.Cout + BN - 1) / BN;
     dim3 grid(a.B * (a.H / TH) * ntn);
     if (a.ev0)
@@ -675,11 +671,7 @@ static hipError_t launch_band_k(const ConvArgs& a, hipStream_t s) {
     constexpr int LDS = 2 * 8 * P64 * 16 + WS * BN * 128;
     static_assert(LDS <= 160 * 1024, "band LDS budget");
     auto k = conv3x3_band_kernel<F16, W, TH, WM, WN, FM, FN, WS>;
-    static bool attr = false;  // opt in to > 64 KiB dynamic LDS once per instantiation
-    if (!attr) {
-        (void)hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
-        attr = true;
-    }
+    if (hipError_t e = lds_opt_in((const void*)k, LDS); e != hipSuccess) return e;  // > 64 KiB dynamic LDS
     const int ntn = (a.Cout + BN - 1) / BN;
     dim3 grid(a.B * (a.H / TH) * ntn);
     if (a.ev0)

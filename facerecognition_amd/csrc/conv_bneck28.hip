@@ -312,12 +312,7 @@ hipError_t launch_bneck28(const Chain17Args& a, bool ds, hipStream_t s) {
     auto k = ds ? (a.f16 ? bneck28_kernel<true, true> : bneck28_kernel<false, true>)
                 : (a.f16 ? bneck28_kernel<true, false> : bneck28_kernel<false, false>);
     const int lds = ds ? Geo<true>::LDS : Geo<false>::LDS;
-    static bool attr[4] = {false, false, false, false};
-    const int ai = (ds ? 2 : 0) + (a.f16 ? 1 : 0);
-    if (!attr[ai]) {
-        (void)hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-        attr[ai] = true;
-    }
+    if (hipError_t e = lds_opt_in((const void*)k, lds); e != hipSuccess) return e;
     if (a.ev0)
         hipExtLaunchKernelGGL(k, dim3(a.B), dim3(64 * NWV), lds, s, (hipEvent_t)a.ev0, (hipEvent_t)a.ev1, 0, a);
     else

@@ -291,11 +291,7 @@ void chain17_pack_block(const bf16_t* rA, int kpA, const bf16_t* r17, int kp17, 
 hipError_t launch_chain17(const Chain17Args& a, hipStream_t s) {
     if (a.B <= 0 || a.nblk <= 0 || !a.x || !a.y || !a.w || !a.bias) return hipErrorInvalidValue;
     auto k = a.f16 ? chain17_kernel<true> : chain17_kernel<false>;
-    static bool attr[2] = {false, false};
-    if (!attr[a.f16 ? 1 : 0]) {
-        (void)hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, CHAIN17_LDS);
-        attr[a.f16 ? 1 : 0] = true;
-    }
+    if (hipError_t e = lds_opt_in((const void*)k, CHAIN17_LDS); e != hipSuccess) return e;
     if (a.ev0)
         hipExtLaunchKernelGGL(k, dim3(a.B), dim3(64 * NWV), CHAIN17_LDS, s, (hipEvent_t)a.ev0, (hipEvent_t)a.ev1, 0, a);
     else

@@ -342,11 +342,7 @@ hipError_t launch_chain35(const Chain35Args& a, hipStream_t s) {
     for (int i = 0; i <= a.nblk; ++i)
         if (!a.io[i]) return hipErrorInvalidValue;
     auto k = a.f16 ? chain35_kernel<true> : chain35_kernel<false>;
-    static bool attr[2] = {false, false};
-    if (!attr[a.f16 ? 1 : 0]) {
-        (void)hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, C35_LDS);
-        attr[a.f16 ? 1 : 0] = true;
-    }
+    if (hipError_t e = lds_opt_in((const void*)k, C35_LDS); e != hipSuccess) return e;
     if (a.ev0)
         hipExtLaunchKernelGGL(k, dim3(a.B), dim3(64 * NWV), C35_LDS, s, (hipEvent_t)a.ev0, (hipEvent_t)a.ev1, 0, a);
     else

@@ -296,11 +296,7 @@ void chain_r50_pack_block(const bf16_t* r1, int kp1, const bf16_t* r2, int kp2, 
 hipError_t launch_chain_r50(const Chain17Args& a, hipStream_t s) {
     if (a.B <= 0 || a.nblk <= 0 || !a.x || !a.y || !a.w || !a.bias) return hipErrorInvalidValue;
     auto k = a.f16 ? chain_r50_kernel<true> : chain_r50_kernel<false>;
-    static bool attr[2] = {false, false};
-    if (!attr[a.f16 ? 1 : 0]) {
-        (void)hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, R50C_LDS);
-        attr[a.f16 ? 1 : 0] = true;
-    }
+    if (hipError_t e = lds_opt_in((const void*)k, R50C_LDS); e != hipSuccess) return e;
     if (a.ev0)
         hipExtLaunchKernelGGL(k, dim3(a.B), dim3(64 * NWV), R50C_LDS, s, (hipEvent_t)a.ev0, (hipEvent_t)a.ev1, 0, a);
     else

@@ -480,12 +480,8 @@ hipError_t launch_conv_direct(const ConvArgs& a, int n_cu, hipStream_t s) {
 #undef D1
     const int ks = a.Kpad / 32, ki = ks <= 2 ? 0 : (ks <= 4 ? 1 : (ks <= 8 ? 2 : 3));
     const KFn k = c.mode == 1 ? kt1[ni][di][ki] : (c.occ == 2 ? kt2[fi][di] : kt[ni][fi][di]);
-    static int attr_lds[32] = {0};  // the largest size set per instantiation
-    const int ai = ((c.occ == 2 ? 2 : 0) + ni) * 8 + fi * 2 + di;
-    if (c.mode == 0 && lds > attr_lds[ai]) {
-        (void)hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-        attr_lds[ai] = lds;
-    }
+    if (c.mode == 0)  // lds varies with the shape: the opt-in keeps the largest size granted per instantiation
+        if (hipError_t e = lds_opt_in((const void*)k, lds); e != hipSuccess) return e;
     if (a.ev0)
         hipExtLaunchKernelGGL(k, dim3(grid), dim3(64 * DNW), lds, s, (hipEvent_t)a.ev0, (hipEvent_t)a.ev1, 0, a, g);
     else

@@ -287,12 +287,7 @@ template <typename G>
 hipError_t launch_img_t(const ConvArgs& a, hipStream_t s) {
     auto k = a.res ? conv_img_kernel<false, true, false, G>
                    : (a.bias9 ? conv_img_kernel<false, false, true, G> : conv_img_kernel<false, false, false, G>);
-    const int v = a.res ? 0 : (a.bias9 ? 1 : 2);
-    static bool attr[3] = {false, false, false};
-    if (!attr[v]) {
-        (void)hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, G::LDS);
-        attr[v] = true;
-    }
+    if (hipError_t e = lds_opt_in((const void*)k, G::LDS); e != hipSuccess) return e;
     const dim3 grid(G::BANDS * a.B);
     if (a.ev0)
         hipExtLaunchKernelGGL(k, grid, dim3(256), G::LDS, s, (hipEvent_t)a.ev0, (hipEvent_t)a.ev1, 0, a);

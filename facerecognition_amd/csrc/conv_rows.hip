@@ -485,12 +485,7 @@ hipError_t launch_conv_rows(const ConvArgs& a, int n_cu, hipStream_t s) {
                 : (a.res ? (act ? conv_rows_kernel<true, 2> : conv_rows_kernel<true, 0>)
                          : (act ? conv_rows_kernel<false, 2> : conv_rows_kernel<false, 0>));
     const int threads = pp ? 512 : 256;
-    const int v = (a.res ? 2 : 0) + (act ? 1 : 0);
-    static bool attr[4] = {false, false, false, false};
-    if (!attr[v]) {
-        (void)hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, ROWS_LDS);
-        attr[v] = true;
-    }
+    if (hipError_t e = lds_opt_in((const void*)k, ROWS_LDS); e != hipSuccess) return e;
     if (a.ev0)
         hipExtLaunchKernelGGL(k, dim3(grid), dim3(threads), ROWS_LDS, s, (hipEvent_t)a.ev0, (hipEvent_t)a.ev1, 0, a, NG,
                               units);

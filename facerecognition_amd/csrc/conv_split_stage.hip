@@ -512,11 +512,7 @@ __global__ __launch_bounds__(64 * NW, 1) void split_stage_kernel(StageArgs p) {
 template <typename G>
 hipError_t launch_split_t(const StageArgs& a, hipStream_t s) {
     auto k = a.f16 ? split_stage_kernel<true, G> : split_stage_kernel<false, G>;
-    static bool attr[2] = {false, false};
-    if (!attr[a.f16 ? 1 : 0]) {
-        (void)hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, G::LDS);
-        attr[a.f16 ? 1 : 0] = true;
-    }
+    if (hipError_t e = lds_opt_in((const void*)k, G::LDS); e != hipSuccess) return e;
     // (no flag reset: the counters run on across launches, see f0 in the kernel)
     const dim3 grid((a.B + 7) / 8 * 8 * G::PARTS);
     if (a.ev0)

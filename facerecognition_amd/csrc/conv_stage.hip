@@ -754,12 +754,7 @@ hipError_t launch_stage(const StageArgs& a, hipStream_t s) {
                       : (a.f16 ? stage13_kernel<true> : stage13_kernel<false>);
     const int lds = v == 1 ? STAGE_LDS : STAGE13_LDS;
     const int threads = v == 2 ? 256 : 64 * SNW;
-    static bool attr[8] = {false, false, false, false, false, false, false, false};
-    const int ai = 2 * v + (a.f16 ? 1 : 0);
-    if (!attr[ai]) {
-        (void)hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-        attr[ai] = true;
-    }
+    if (hipError_t e = lds_opt_in((const void*)k, lds); e != hipSuccess) return e;
     if (a.ev0)
         hipExtLaunchKernelGGL(k, dim3(a.B), dim3(threads), lds, s, (hipEvent_t)a.ev0, (hipEvent_t)a.ev1, 0, a);
     else

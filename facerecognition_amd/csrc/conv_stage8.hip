@@ -328,11 +328,7 @@ void stage8_pack_weights(const uint8_t* rows, int Kpad8, uint8_t* out) {
 
 hipError_t launch_stage8(const StageArgs& a, hipStream_t s) {
     if (a.B <= 0 || !a.w || !a.wscale || !a.ep || !a.slope || a.f16) return hipErrorInvalidValue;
-    static bool attr = false;
-    if (!attr) {
-        (void)hipFuncSetAttribute((const void*)stage8_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, LDS8);
-        attr = true;
-    }
+    if (hipError_t e = lds_opt_in((const void*)stage8_kernel, LDS8); e != hipSuccess) return e;
     if (a.ev0)
         hipExtLaunchKernelGGL(stage8_kernel, dim3(a.B), dim3(64 * NW), LDS8, s, (hipEvent_t)a.ev0, (hipEvent_t)a.ev1, 0, a);
     else

@@ -364,12 +364,7 @@ hipError_t launch_stem160(const Stem160Args& a, hipStream_t s) {
     const bool u8 = a.u8 != nullptr;
     auto k = a.f16 ? (u8 ? stem160_kernel<true, true> : stem160_kernel<true, false>)
                    : (u8 ? stem160_kernel<false, true> : stem160_kernel<false, false>);
-    static bool attr[4] = {false, false, false, false};
-    const int ai = (a.f16 ? 2 : 0) + (u8 ? 1 : 0);
-    if (!attr[ai]) {
-        (void)hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, STEM_LDS);
-        attr[ai] = true;
-    }
+    if (hipError_t e = lds_opt_in((const void*)k, STEM_LDS); e != hipSuccess) return e;
     if (a.ev0)
         hipExtLaunchKernelGGL(k, dim3(a.B), dim3(256), STEM_LDS, s, (hipEvent_t)a.ev0, (hipEvent_t)a.ev1, 0, a);
     else

@@ -266,12 +266,7 @@ hipError_t launch_stem_r50(const StemR50Args& a, hipStream_t s) {
     if ((size_t)a.B * IH * IH * 16 >= 0x80000000ull) return hipErrorInvalidValue;  // 31-bit buffer offsets
     auto k = a.u8 ? (a.f16 ? stem_r50_kernel<true, true> : stem_r50_kernel<false, true>)
                   : (a.f16 ? stem_r50_kernel<true, false> : stem_r50_kernel<false, false>);
-    static bool attr[4] = {false, false, false, false};
-    const int ai = (a.u8 ? 2 : 0) + (a.f16 ? 1 : 0);
-    if (!attr[ai]) {
-        (void)hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, SR50_LDS);
-        attr[ai] = true;
-    }
+    if (hipError_t e = lds_opt_in((const void*)k, SR50_LDS); e != hipSuccess) return e;
     if (a.ev0)
         hipExtLaunchKernelGGL(k, dim3(a.B), dim3(64 * NWV), SR50_LDS, s, (hipEvent_t)a.ev0, (hipEvent_t)a.ev1, 0, a);
     else

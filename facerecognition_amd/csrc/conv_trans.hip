@@ -375,11 +375,7 @@ hipError_t launch_trans(const TransArgs& a, hipStream_t s) {
         !a.slope1 || !a.b2)
         return hipErrorInvalidValue;
     auto k = a.f16 ? trans_kernel<true> : trans_kernel<false>;
-    static bool attr[2] = {false, false};
-    if (!attr[a.f16 ? 1 : 0]) {
-        (void)hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, TRANS_LDS);
-        attr[a.f16 ? 1 : 0] = true;
-    }
+    if (hipError_t e = lds_opt_in((const void*)k, TRANS_LDS); e != hipSuccess) return e;
     if (a.ev0)
         hipExtLaunchKernelGGL(k, dim3(a.B), dim3(256), TRANS_LDS, s, (hipEvent_t)a.ev0, (hipEvent_t)a.ev1, 0, a);
     else

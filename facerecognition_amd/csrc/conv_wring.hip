@@ -360,11 +360,7 @@ hipError_t launch_kss(const ConvArgs& a, hipStream_t s) {
     const int tiles_m = (a.M + BM - 1) / BM, tiles_n = a.Cout / Gm::BN;
     auto k = a.f16 ? conv_wring_kernel<true, KSS, NW> : conv_wring_kernel<false, KSS, NW>;
     const int lds = Gm::LDS;
-    static bool attr[2] = {false, false};
-    if (!attr[a.f16 ? 1 : 0]) {
-        (void)hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-        attr[a.f16 ? 1 : 0] = true;
-    }
+    if (hipError_t e = lds_opt_in((const void*)k, lds); e != hipSuccess) return e;
     const dim3 grid((unsigned)(tiles_m * tiles_n));
     if (a.ev0)
         hipExtLaunchKernelGGL(k, grid, dim3(64 * NW), lds, s, (hipEvent_t)a.ev0, (hipEvent_t)a.ev1, 0, a, tiles_m);

@@ -1,6 +1,6 @@
 // frhip engine: C-ABI handle, weight-blob loader, static per-arch forward plans and the
 // gallery/match entry points.  See include/frhip.h for the boundary contract and
-// DESIGN.md for the data layout.
+// DESIGN.md for the data layout.  The fused stages of a plan (their kinds, packers, launches) are in stages.cpp.
 //
 // The forward plans restate the reference backbones as a list of fused ops:
 //   FR_ARCH_RESNET50_ARCFACE  models/arcface/arcface_model.py:118-132 + head :192-196
@@ -19,8 +19,7 @@
 #include <unordered_map>
 #include <vector>
 
-#include "../../include/frhip.h"
-#include "kernels.h"
+#include "engine_internal.h"
 
 namespace fr {
 static thread_local std::string g_err;
@@ -55,6 +54,33 @@ int ab_int(const char* key, int dflt) {
     const char* v = ab_str(key);
     return v ? atoi(v) : dflt;
 }
+
+hipError_t lds_opt_in(const void* kernel, int bytes) {
+    struct Grant { const void* kernel; int device, bytes; };
+    static std::mutex mu;
+    static std::vector<Grant> grants;  // a few dozen entries: one per kernel instantiation that ran, per device
+    int device = 0;
+    hipError_t e = hipGetDevice(&device);
+    if (e != hipSuccess) return e;
+    std::lock_guard<std::mutex> lk(mu);
+    auto g = std::find_if(grants.begin(), grants.end(), [&](const Grant& x) { return x.kernel == kernel && x.device == device; });
+    if (g != grants.end() && g->bytes >= bytes) return hipSuccess;
+    e = hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
+    if (e != hipSuccess) return e;
+    if (g != grants.end()) g->bytes = bytes;
+    else grants.push_back({kernel, device, bytes});
+    return hipSuccess;
+}
+
+int dev_alloc(void** p, size_t bytes) {
+    if (bytes == 0) bytes = 16;
+    hipError_t e = hipMalloc(p, bytes);
+    if (e != hipSuccess) {
+        set_error(std::string("hipMalloc(") + std::to_string(bytes) + "): " + hipGetErrorString(e));
+        return e == hipErrorOutOfMemory ? FR_ERR_OOM : FR_ERR_HIP;
+    }
+    return FR_OK;
+}
 }  // namespace fr
 
 using namespace fr;
@@ -66,223 +92,10 @@ struct HostT {
     std::vector<float> v;
 };
 
-struct DevConvW {
-    bf16_t* w = nullptr;
-    float* bias = nullptr;
-    float* slope = nullptr;
-    float* aff_s = nullptr;
-    float* aff_b = nullptr;
-    float* bias9 = nullptr;  // [9][Npad] border-class bias (input BN folded into a 3x3/s1/p1 conv)
-    bf16_t* wimg = nullptr;  // conv_img.hip K-step slice images (convs its kernels apply to)
-    float* negf = nullptr;   // conv_img / conv_rows: [Npad] activation negative-side factor (slope / 0 / 1)
-    bf16_t* wrows = nullptr; // conv_rows.hip weight image (rows_pack_weights)
-    float* ep = nullptr;     // conv_rows.hip: [9][Npad] bias per border class
-    bf16_t* wring = nullptr; // conv_wring.hip substep images (wring_pack_weights)
-    uint8_t* w8 = nullptr;   // FR_DTYPE_FP8: e4m3 [Npad][Kpad8] + per-channel scale
-    float* wscale = nullptr;
-    int Cout = 0, Kh = 1, Kw = 1, Cin = 0, K = 0, Npad = 0, Kpad = 0, Kpad8 = 0;
-    int K1 = 0, C2 = 0;  // K-concatenated 1x1 projection: K = K1 + C2 (ConvArgs::x2), else K1 = K, C2 = 0
-};
-
-struct TensorDesc {
-    int H, W, C;
-    bf16_t* dev = nullptr;
-    std::string name;  // oracle module whose output this tensor equals ("" = internal)
-    bool f16 = false;  // stored as f16 in a bf16 plan (IRV1's high-resolution stem, build_irv1)
-};
-
-enum OpKind { OP_PRE, OP_CONV, OP_MAXPOOL, OP_AVGPOOL, OP_HEAD, OP_STAGE };
-
-struct Op {
-    OpKind kind;
-    int in = -1, in_off = 0, cin = 0;
-    int out = -1, out_off = 0;
-    int res = -1, res_off = 0;
-    int out2 = -1;
-    int kh = 1, kw = 1, sh = 1, sw = 1, ph = 0, pw = 0;
-    int act = 0;
-    int wi = -1;
-    int pk = 0, ps = 0, pp = 0;
-    int stage = -1;  // OP_STAGE: its StageRec; OP_CONV: the stage that covers it (skipped when stages run)
-    int x2 = -1, x2_off = 0, st2 = 1;  // OP_CONV with a K-concatenated downsample: its input tensor, stride
-    bool fuse_stem = false;  // OP_PRE of IResNet100: u8 input runs preprocess + the next (stem) conv fused
-    int grp = -1;    // index into the stage plan (stage_plan)
-};
-
-// One LDS-resident stage: the stride-1 blocks of a 14x14x256 layer (conv_stage.hip: one workgroup per
-// image, parts = 1) or of a 28x28x128 / 56x56x64 layer (conv_split_stage.hip: parts = 2 / 4 workgroups
-// per image).
-struct StageRec {
-    int in = -1, out = -1, nblk = 0;
-    int parts = 1, H = 14, C = 256;
-    std::vector<int> conv_ops;            // member OP_CONV indices, conv1/conv2 alternating
-    std::vector<int> t_tensors, x_tensors;  // per block: conv1 output, block output
-    bf16_t* w = nullptr;                  // packed K-step weight images
-    StageConv* table = nullptr;           // [2*nblk]
-    float* ep = nullptr;                  // [2*nblk][9][256] epilogue bias per border class
-    float* slope = nullptr;               // [2*nblk][256] negative-side factor (slope / 0 / 1)
-    bf16_t** dbg = nullptr;               // [2*nblk] device pointer table: x outputs then t outputs
-    bool fp8 = false;                     // e4m3 stage (conv_stage8.hip): the members carry .wscale
-    uint8_t* w8 = nullptr;                // fp8: stage8_pack_weights images of all convs
-    float* wscale = nullptr;              // fp8: [2*nblk][256] per-channel weight scales
-    // fused transition block (conv_trans.hip, IResNet100 layer1.0): conv_ops = {conv1, conv2 + downsample}
-    bool trans = false;
-    bf16_t* tw1 = nullptr;                // trans_pack_weights images of conv1 / conv2 + downsample
-    bf16_t* tw2 = nullptr;
-    float* tep1 = nullptr;                // [9][64] conv1 bias per border class
-    float* tsl1 = nullptr;                // [64] conv1 PReLU slopes
-    float* tb2 = nullptr;                 // [64] conv2 + downsample bias
-    // layer3 stage tail (round 5): the conv after the stage (IResNet100 layer4.0.conv1, 3x3/s1 256 -> 512 +
-    // border-class bias + PReLU) runs on the stage's final patch (conv_stage.hip run_tail); its weights and
-    // tables follow the blocks' as two 256-channel halves; tail_op is also the last entry of conv_ops
-    int tail_op = -1;
-    // IRV1 repeat_2 as one launch (chain 17, conv_chain.hip): conv_ops = per block {branch1.0 + branch0, 1x7, 7x1,
-    // conv2d}; repeat_1 (chain 35, conv_chain35.hip): per block {branch1.0 + branch2.0 + branch0, branch1.1, branch2.1,
-    // branch2.2, conv2d}, x_tensors = the block outputs; ResNet-50 layer3.1 .. 3.5 (chain 50, conv_chain_r50.hip):
-    // per block {conv1, conv2, conv3}; ResNet-50 layer1 (chain 28, conv_bneck28.hip, one launch per block): per block
-    // {conv1, conv2, conv3}, x_tensors = the block outputs; bn_ds: the first is layer1.0 (conv3 + K-concatenated
-    // downsample); ResNet-50 stem (chain 56, conv_stem_r50.hip): {conv1, maxpool}
-    int chain = 0;
-    bool bn_ds = false;
-    bf16_t* cw = nullptr;                 // the packed weights of all blocks
-    float* cbias = nullptr;               // the member convs' biases
-    // IRV1 stem as one launch (conv_stem160.hip): conv_ops = {conv2d_1a, conv2d_2a, conv2d_2b, maxpool_3a}
-    bool stem = false;
-};
-
 int round_up(int x, int m) { return (x + m - 1) / m * m; }
 
 constexpr size_t FR_MAX_SPLIT_STAGES = 6;  // stage ops per plan (at most one per residual layer + the transition)
 constexpr int FR_SPLITK_TILES = 1 << 16;   // in-launch split-K tile counters per handle
-
-}  // namespace
-
-struct fr_handle {
-    int device = 0, arch = 0, dtype = 0;
-    std::mutex mu;
-    bool loaded = false;
-    int in_size = 112, embed_dim = 512;
-    std::vector<TensorDesc> tensors;
-    std::vector<Op> ops;
-    std::vector<DevConvW> convw;
-    std::vector<void*> weight_allocs;
-    int max_batch = 0;
-    std::vector<void*> act_allocs;
-    float* partial = nullptr;
-    size_t partial_floats = 0;
-    int* splitk_cnt = nullptr;  // [FR_SPLITK_TILES] in-launch split-K arrival counters (conv_igemm), zero between launches
-    bool splitk_inlaunch = true;  // FR_OPT_SPLITK_INLAUNCH
-    bool inlaunch_used = false;   // an in-launch split-K conv has run (the per-forward counter memset is needed)
-    // gallery
-    float* gallery = nullptr;
-    int64_t g_rows = 0;
-    int64_t g_cap = 0;       // rows allocated (fr_gallery_write grows it geometrically)
-    int g_dim = 0;
-    int64_t g_base = 0;
-    bf16_t* g_hi = nullptr;  // bf16 hi/lo split of the prepared gallery in chunk order (match_x3.hip), N >= X3_MIN_ROWS
-    int* match_fb = nullptr;  // device counter of exact-rescan fallbacks (fr_debug_match_fallbacks)
-    bool match_exact = false; // FR_OPT_MATCH_EXACT: always the f32-MFMA kernel
-    int64_t x3_min_rows = X3_MIN_ROWS;  // FR_OPT_X3_MIN_ROWS
-    float* cand_s = nullptr;
-    int32_t* cand_i = nullptr;
-    size_t cand_cap = 0;
-    // per-kernel-class event timing (fr_prof_*): events recorded on the launching stream
-    struct ProfRec { std::string cls; hipEvent_t a, b; double flops, bytes; };
-    struct ProfAcc { double ms = 0; int64_t launches = 0; double flops = 0, bytes = 0; };
-    bool prof = false;
-    int prof_stride = 1;        // time every n-th matching launch (sampling keeps the overhead small)
-    uint64_t prof_seen = 0;
-    std::string prof_only;  // non-empty: time only this kernel class
-    std::vector<hipEvent_t> ev_free;
-    std::vector<ProfRec> prof_pending;
-    std::vector<std::pair<std::string, ProfAcc>> prof_acc;
-    // forward replays as hipGraphs, keyed by the call's pointers / shape (captured on the second call
-    // with a key; the first call runs eagerly and warms per-kernel attributes)
-    struct GraphEnt { const void* in; float* out; int fmt, B, flags, slot; hipGraphExec_t exec; bool no_graph; uint64_t used; };
-    // graph-slot timing (fr_prof_slots): an event pair per slot around one launch of one kernel class --
-    // slot i times launch i mod (the class's launches per forward) -- captured into the graph of that slot,
-    // so timed steps replay graphs and still time the class
-    std::string slot_class;
-    std::vector<std::pair<hipEvent_t, hipEvent_t>> slot_events;
-    std::vector<std::pair<double, double>> slot_work;  // the timed launch's algorithmic FLOPs and bytes
-    int slot = -1;         // the slot the next forward captures / replays (-1: none)
-    bool slot_done = false;  // the slot's pair is placed in the current forward
-    int slot_seen = 0;     // launches of slot_class so far in the current forward
-    int slot_nl = 0;       // launches of slot_class per forward (learned by the first slot forward)
-    std::vector<GraphEnt> graphs;
-    hipStream_t cap_stream = nullptr;
-    // branch-parallel capture (forward_graph): a second capturing stream and one event per op
-    hipStream_t aux_stream = nullptr;
-    std::vector<hipEvent_t> op_events;
-    bool ms_on = false;
-    uint64_t tick = 0;
-    // per-shape igemm tile autotuning (numerically invisible: every tile accumulates K in the same
-    // order; split-K choices stay with the cost model)
-    struct Tuned { int key[13]; int tile, split; };  // the measured kernel choice per conv shape (tune_conv)
-    std::vector<Tuned> tuned;
-    std::vector<int> tuned_batches;
-    struct StageMeas { int stage, B, run; float t_stage, t_conv; };  // measured stage-vs-per-conv choice per batch
-    std::vector<StageMeas> stage_meas;
-    bool tuning = false;
-    // LDS-resident stage kernels (fr_set_option FR_OPT_STAGE / FR_OPT_KEEP_INTERMEDIATES)
-    std::vector<StageRec> stages;
-    // FaceNet projection (Linear(512, d) + F.normalize after IRV1's own L2; facenet_model.py:20-23,32-35)
-    float* proj_w = nullptr;
-    float* proj_b = nullptr;
-    int proj_d = 0;
-    float* emb_pre = nullptr;  // [max_batch][512] IRV1 output before the projection
-    float* amax = nullptr;     // FR_DTYPE_FP8: per-tensor max |x| of the current forward [ntensors]
-    std::vector<char> need_amax;  // per tensor: the input of a per-conv e4m3 conv (its producer writes amax)
-    bf16_t* stage_xchg = nullptr;  // split-stage boundary rows (split_stage_xchg_elems(max_batch), reserve)
-    int* stage_flags = nullptr;    // split-stage progress counters [stage][max_batch][4], never reset
-    int* stage_spin = nullptr;     // split-stage bounded-wait overruns (fr_debug_stage_timeouts)
-    // split-stage failure reporting: a host-mapped flag the kernel sets when a halo wait runs out
-    // (fail_host: host view, fail_dev: the device alias the kernel stores to)
-    int* fail_host = nullptr;
-    int* fail_dev = nullptr;
-    int spin_limit = 0;            // FR_OPT_STAGE_SPIN_LIMIT (0: the kernel's default, < 0: every wait runs out)
-    int stage_variant = 0;         // FR_OPT_STAGE_VARIANT (1: the legacy 14-fragment layer3 stage kernel, 2: one wave per SIMD,
-                                   // 3: waves split by output channel)
-    bool no_split = false;         // re-run of a failed forward: split stages off
-    int64_t stage_reruns = 0;      // forwards re-run on the per-conv path after a run-out wait
-    hipEvent_t chk_ev = nullptr;   // completion of the last synchronous-checked forward
-    hipEvent_t async_ev = nullptr; // completion of the last FR_EMBED_ASYNC split-stage forward ...
-    bool async_pending = false;    // ... not yet waited for (its failure is not yet latched)
-    bool split_registered = false; // counted in the per-device split-stage handle registry (DevSerial)
-    int stage_mode = 1;       // FR_OPT_STAGE: 0 off, 1 auto (stage_runs), 2 always
-    int stage_min_fill = 80;  // FR_OPT_STAGE_MIN_FILL (percent)
-    int n_cu = 256;
-    bool keep_inter = false;
-    // FR_OPT_BATCH_INVARIANT: every kernel choice sums K in the implicit GEMM's order (no split-K, no stage /
-    // transition kernel, a fixed head split), so a face's embedding does not depend on its batch
-    bool invariant = false;
-    int fused_mask = 127;  // FR_OPT_FUSED_MASK
-    const uint8_t* fwd_u8 = nullptr;  // the current forward's u8 crops when the IRV1 fused stem prepares them itself
-};
-
-namespace {
-
-// ------------------------------------------------------------------ device memory helpers
-int dev_alloc(void** p, size_t bytes) {
-    if (bytes == 0) bytes = 16;
-    hipError_t e = hipMalloc(p, bytes);
-    if (e != hipSuccess) {
-        set_error(std::string("hipMalloc(") + std::to_string(bytes) + "): " + hipGetErrorString(e));
-        return e == hipErrorOutOfMemory ? FR_ERR_OOM : FR_ERR_HIP;
-    }
-    return FR_OK;
-}
-
-template <class T>
-int upload(fr_handle* h, T** dst, const std::vector<T>& src) {
-    void* p = nullptr;
-    int rc = dev_alloc(&p, src.size() * sizeof(T));
-    if (rc) return rc;
-    h->weight_allocs.push_back(p);
-    FR_HIP_CHECK(hipMemcpy(p, src.data(), src.size() * sizeof(T), hipMemcpyHostToDevice));
-    *dst = (T*)p;
-    return FR_OK;
-}
 
 void drop_graphs(fr_handle* h) {
     if (h->graphs.empty()) return;
@@ -649,353 +462,32 @@ struct Builder {
         if ((rc = upload(h, &h->proj_b, bb->v))) return;
         h->proj_d = (int)w->dims[0];
     }
+
+    // A fused stage beside its member ops (stages.cpp).  Opening pushes the OP_STAGE op, ahead of the members the
+    // caller emits next, and returns its index.
+    int open_stage() {
+        Op op;
+        op.kind = OP_STAGE;
+        op.stage = (int)h->stages.size();
+        h->ops.push_back(op);
+        return (int)h->ops.size() - 1;
+    }
+    // Closing takes the finished record (its members in conv_ops): the members point at the stage, the kind's
+    // weight packer runs, and the record joins the plan.  fits = false: the members do not have the fused kernel's
+    // shapes, so the plan keeps the member ops only.
+    void close_stage(int st_op, StageRec& r, bool fits = true) {
+        if (rc) return;
+        if (!fits) {
+            h->ops.erase(h->ops.begin() + st_op);
+            for (auto& op : h->ops)
+                if (op.kind == OP_STAGE && op.stage >= (int)h->stages.size()) --op.stage;
+            return;
+        }
+        for (int oi : r.conv_ops) h->ops[oi].stage = h->ops[st_op].stage;
+        rc = pack_stage(h, r);
+        h->stages.push_back(r);
+    }
 };
-
-// Packs a stage's weights (from the member convs' [Npad][Kpad] device images) and its epilogue table.
-int build_stage(fr_handle* h, StageRec& r) {
-    const int nconv = 2 * r.nblk, C = r.C;
-    const int ntail = r.tail_op >= 0 ? 2 : 0;  // the tail's two 256-channel halves follow the blocks' convs
-    const int nall = nconv + ntail;
-    const size_t wbytes = r.fp8 ? 0 : (r.parts > 1 ? split_stage_weight_bytes(C, nall) : stage_weight_bytes(nall));
-    std::vector<bf16_t> packed(wbytes / sizeof(bf16_t));
-    std::vector<uint8_t> packed8(r.fp8 ? stage8_weight_bytes(nconv) : 0);
-    std::vector<float> wsc(r.fp8 ? (size_t)nconv * C : 0);
-    std::vector<StageConv> tab(nconv);
-    std::vector<float> ep((size_t)nall * 9 * C, 0.f), sl((size_t)nall * C, 0.f);
-    const size_t per = packed.size() / nall;
-    for (int c = 0; c < nconv; ++c) {
-        const Op& op = h->ops[r.conv_ops[c]];
-        const DevConvW& cw = h->convw[op.wi];
-        if (cw.Cout != C || cw.Npad < C || cw.Kh != 3 || cw.Kw != 3 || cw.Cin != C) {
-            set_error("plan: stage member conv is not 3x3 " + std::to_string(C) + "->" + std::to_string(C));
-            return FR_ERR_ARG;
-        }
-        // the stage kernel's epilogues are specialised: conv1 = bias + PReLU, conv2 = bias + identity
-        if ((c % 2 == 0 && (op.act != 2 || !cw.slope)) || (c % 2 == 1 && (op.act != 0 || op.res < 0))) {
-            set_error("plan: stage member conv has an unexpected activation / residual");
-            return FR_ERR_ARG;
-        }
-        if (r.fp8) {
-            if (!cw.w8 || !cw.wscale || cw.Kpad8 != 9 * C || C != 256) {
-                set_error("plan: fp8 stage member conv without e4m3 weights");
-                return FR_ERR_ARG;
-            }
-            std::vector<uint8_t> rows8((size_t)cw.Npad * cw.Kpad8);
-            FR_HIP_CHECK(hipMemcpy(rows8.data(), cw.w8, rows8.size(), hipMemcpyDeviceToHost));
-            stage8_pack_weights(rows8.data(), cw.Kpad8, packed8.data() + (size_t)c * (packed8.size() / nconv));
-            FR_HIP_CHECK(hipMemcpy(wsc.data() + (size_t)c * C, cw.wscale, C * sizeof(float), hipMemcpyDeviceToHost));
-        } else {
-            std::vector<bf16_t> rows((size_t)cw.Npad * cw.Kpad);
-            FR_HIP_CHECK(hipMemcpy(rows.data(), cw.w, rows.size() * sizeof(bf16_t), hipMemcpyDeviceToHost));
-            if (r.parts > 1) split_stage_pack_weights(rows.data(), cw.Kpad, C, packed.data() + c * per);
-            else stage_pack_weights(rows.data(), cw.Kpad, C, packed.data() + c * per);
-        }
-        tab[c].bias = cw.bias9 ? nullptr : cw.bias;
-        tab[c].bias9 = cw.bias9;
-        tab[c].slope = cw.slope;
-        tab[c].act = op.act;
-        // the epilogue's per-class bias: bias9 (which already carries the whole bias) or bias x 9
-        // (bias9 rows are Npad apart)
-        float* e = ep.data() + (size_t)c * 9 * C;
-        if (cw.bias9) {
-            for (int k = 0; k < 9; ++k)
-                FR_HIP_CHECK(hipMemcpy(e + k * C, cw.bias9 + (size_t)k * cw.Npad, C * sizeof(float), hipMemcpyDeviceToHost));
-        } else if (cw.bias) {
-            FR_HIP_CHECK(hipMemcpy(e, cw.bias, C * sizeof(float), hipMemcpyDeviceToHost));
-            for (int k = 1; k < 9; ++k) std::copy(e, e + C, e + k * C);
-        }
-        // negative-side factor of the activation: PReLU slope, 0 for ReLU, 1 for none
-        float* f = sl.data() + (size_t)c * C;
-        if (op.act == 2 && cw.slope)
-            FR_HIP_CHECK(hipMemcpy(f, cw.slope, C * sizeof(float), hipMemcpyDeviceToHost));
-        else
-            std::fill(f, f + C, op.act == 1 ? 0.f : 1.f);
-    }
-    if (ntail) {  // rows [C half, C half + C) of the tail conv (3x3 C -> 2C): bias9 halves, PReLU slopes
-        const Op& op = h->ops[r.tail_op];
-        const DevConvW& cw = h->convw[op.wi];
-        std::vector<bf16_t> rows((size_t)cw.Npad * cw.Kpad);
-        FR_HIP_CHECK(hipMemcpy(rows.data(), cw.w, rows.size() * sizeof(bf16_t), hipMemcpyDeviceToHost));
-        std::vector<float> b9((size_t)9 * cw.Npad, 0.f), slope(cw.Cout);
-        if (cw.bias9) {
-            FR_HIP_CHECK(hipMemcpy(b9.data(), cw.bias9, b9.size() * sizeof(float), hipMemcpyDeviceToHost));
-        } else if (cw.bias) {
-            FR_HIP_CHECK(hipMemcpy(b9.data(), cw.bias, cw.Npad * sizeof(float), hipMemcpyDeviceToHost));
-            for (int k = 1; k < 9; ++k) std::copy(b9.begin(), b9.begin() + cw.Npad, b9.begin() + (size_t)k * cw.Npad);
-        }
-        FR_HIP_CHECK(hipMemcpy(slope.data(), cw.slope, cw.Cout * sizeof(float), hipMemcpyDeviceToHost));
-        for (int hf = 0; hf < 2; ++hf) {
-            const int c = nconv + hf;
-            if (r.parts > 1) split_stage_pack_weights(rows.data() + (size_t)hf * C * cw.Kpad, cw.Kpad, C, packed.data() + c * per);
-            else stage_pack_weights(rows.data() + (size_t)hf * C * cw.Kpad, cw.Kpad, C, packed.data() + c * per);
-            for (int k = 0; k < 9; ++k)
-                std::copy(b9.begin() + (size_t)k * cw.Npad + hf * C, b9.begin() + (size_t)k * cw.Npad + hf * C + C,
-                          ep.begin() + ((size_t)c * 9 + k) * C);
-            std::copy(slope.begin() + hf * C, slope.begin() + hf * C + C, sl.begin() + (size_t)c * C);
-        }
-    }
-    int rc = r.fp8 ? upload(h, &r.w8, packed8) : upload(h, &r.w, packed);
-    if (rc) return rc;
-    if (r.fp8 && (rc = upload(h, &r.wscale, wsc))) return rc;
-    rc = upload(h, &r.table, tab);
-    if (rc) return rc;
-    if ((rc = upload(h, &r.ep, ep))) return rc;
-    if ((rc = upload(h, &r.slope, sl))) return rc;
-    void* d = nullptr;
-    if ((rc = dev_alloc(&d, (size_t)nconv * sizeof(bf16_t*)))) return rc;
-    h->weight_allocs.push_back(d);
-    r.dbg = (bf16_t**)d;
-    if (r.parts > 1 && !h->stage_spin) {
-        if ((rc = dev_alloc(&d, sizeof(int)))) return rc;
-        h->weight_allocs.push_back(d);
-        h->stage_spin = (int*)d;
-        FR_HIP_CHECK(hipMemset(h->stage_spin, 0, sizeof(int)));
-    }
-    return FR_OK;
-}
-
-// Device pointer table of a stage's intermediate tensors (filled after every activation reserve).
-int fill_stage_dbg(fr_handle* h) {
-    for (auto& r : h->stages) {
-        if (r.trans || r.chain || r.stem) continue;  // no intermediates: the member convs run when they are kept
-        std::vector<bf16_t*> p(2 * r.nblk);
-        for (int i = 0; i < r.nblk; ++i) {
-            p[i] = h->tensors[r.x_tensors[i]].dev;
-            p[r.nblk + i] = h->tensors[r.t_tensors[i]].dev;
-        }
-        FR_HIP_CHECK(hipMemcpy(r.dbg, p.data(), p.size() * sizeof(bf16_t*), hipMemcpyHostToDevice));
-    }
-    return FR_OK;
-}
-
-// Packs a fused transition block (conv_trans.hip) from its member convs' device weights.
-int build_trans(fr_handle* h, StageRec& r) {
-    const DevConvW& c1 = h->convw[h->ops[r.conv_ops[0]].wi];
-    const DevConvW& c2 = h->convw[h->ops[r.conv_ops[1]].wi];
-    if (c1.K != 576 || c2.K != 640 || c2.K1 != 576 || c2.C2 != 64 || c1.Cout != 64 || c2.Cout != 64 || !c1.slope ||
-        (!c1.bias9 && !c1.bias) || !c2.bias) {
-        set_error("plan: transition block members do not match the fused kernel");
-        return FR_ERR_ARG;
-    }
-    void* q = nullptr;
-    int rc = dev_alloc(&q, trans_packed_elems(c1.K) * sizeof(bf16_t));
-    if (rc) return rc;
-    h->weight_allocs.push_back(q);
-    r.tw1 = (bf16_t*)q;
-    if ((rc = dev_alloc(&q, trans_packed_elems(c2.K) * sizeof(bf16_t)))) return rc;
-    h->weight_allocs.push_back(q);
-    r.tw2 = (bf16_t*)q;
-    FR_HIP_CHECK(trans_pack_weights(c1.w, c1.Kpad, c1.K, r.tw1, 0));
-    FR_HIP_CHECK(trans_pack_weights(c2.w, c2.Kpad, c2.K, r.tw2, 0));
-    FR_HIP_CHECK(hipDeviceSynchronize());
-    std::vector<float> ep(9 * 64), sl(64), b2(64);
-    if (c1.bias9) {
-        for (int k = 0; k < 9; ++k)
-            FR_HIP_CHECK(hipMemcpy(ep.data() + k * 64, c1.bias9 + (size_t)k * c1.Npad, 64 * sizeof(float), hipMemcpyDeviceToHost));
-    } else {
-        FR_HIP_CHECK(hipMemcpy(ep.data(), c1.bias, 64 * sizeof(float), hipMemcpyDeviceToHost));
-        for (int k = 1; k < 9; ++k) std::copy(ep.begin(), ep.begin() + 64, ep.begin() + k * 64);
-    }
-    FR_HIP_CHECK(hipMemcpy(sl.data(), c1.slope, 64 * sizeof(float), hipMemcpyDeviceToHost));
-    FR_HIP_CHECK(hipMemcpy(b2.data(), c2.bias, 64 * sizeof(float), hipMemcpyDeviceToHost));
-    if ((rc = upload(h, &r.tep1, ep))) return rc;
-    if ((rc = upload(h, &r.tsl1, sl))) return rc;
-    return upload(h, &r.tb2, b2);
-}
-
-// Packs IRV1 repeat_2's member convs (per block: branch1.0 + branch0 as one 1x1 896 -> 256, the 1x7 and 7x1
-// 128 -> 128, conv2d 256 -> 896 with the residual) into conv_chain.hip's per-wave streams and bias table.
-int build_chain17(fr_handle* h, StageRec& r) {
-    const int nblk = r.nblk;
-    if ((int)r.conv_ops.size() != 4 * nblk) {
-        set_error("plan: chain member count");
-        return FR_ERR_ARG;
-    }
-    std::vector<bf16_t> packed(chain17_weight_elems(nblk));
-    std::vector<float> bias(chain17_bias_floats(nblk), 0.f);
-    for (int blk = 0; blk < nblk; ++blk) {
-        const Op* op[4];
-        const DevConvW* cw[4];
-        std::vector<bf16_t> rows[4];
-        for (int k = 0; k < 4; ++k) {
-            op[k] = &h->ops[r.conv_ops[4 * blk + k]];
-            cw[k] = &h->convw[op[k]->wi];
-            if (cw[k]->w8 || !cw[k]->bias || op[k]->act != 1) {
-                set_error("plan: chain member conv is not bf16 / f16 + bias + ReLU");
-                return FR_ERR_ARG;
-            }
-            rows[k].resize((size_t)cw[k]->Npad * cw[k]->Kpad);
-            FR_HIP_CHECK(hipMemcpy(rows[k].data(), cw[k]->w, rows[k].size() * sizeof(bf16_t), hipMemcpyDeviceToHost));
-        }
-        const bool shapes = cw[0]->Cout == 256 && cw[0]->K == 896 && cw[0]->Kh == 1 && cw[0]->Kw == 1 &&
-                            cw[1]->Cout == 128 && cw[1]->K == 896 && cw[1]->Kh == 1 && cw[1]->Kw == 7 &&
-                            cw[2]->Cout == 128 && cw[2]->K == 896 && cw[2]->Kh == 7 && cw[2]->Kw == 1 &&
-                            cw[3]->Cout == 896 && cw[3]->K == 256 && cw[3]->Kh == 1 && cw[3]->Kw == 1 &&
-                            op[3]->res >= 0 && op[3]->res_off == 0 && op[0]->res < 0 && op[1]->res < 0 && op[2]->res < 0;
-        if (!shapes) {
-            set_error("plan: chain member convs do not have Block17's shapes");
-            return FR_ERR_ARG;
-        }
-        chain17_pack_block(rows[0].data(), cw[0]->Kpad, rows[1].data(), cw[1]->Kpad, rows[2].data(), cw[2]->Kpad,
-                           rows[3].data(), cw[3]->Kpad, blk, nblk, packed.data());
-        // [A = branch1.0 | B = 1x7 | C = 7x1 | D = branch0 | E = conv2d]
-        float* t = bias.data() + (size_t)blk * 1408;
-        std::vector<float> b0(256), b3(896), b1(128), b2(128);
-        FR_HIP_CHECK(hipMemcpy(b0.data(), cw[0]->bias, 256 * sizeof(float), hipMemcpyDeviceToHost));
-        FR_HIP_CHECK(hipMemcpy(b1.data(), cw[1]->bias, 128 * sizeof(float), hipMemcpyDeviceToHost));
-        FR_HIP_CHECK(hipMemcpy(b2.data(), cw[2]->bias, 128 * sizeof(float), hipMemcpyDeviceToHost));
-        FR_HIP_CHECK(hipMemcpy(b3.data(), cw[3]->bias, 896 * sizeof(float), hipMemcpyDeviceToHost));
-        std::copy(b0.begin(), b0.begin() + 128, t);
-        std::copy(b1.begin(), b1.end(), t + 128);
-        std::copy(b2.begin(), b2.end(), t + 256);
-        std::copy(b0.begin() + 128, b0.end(), t + 384);
-        std::copy(b3.begin(), b3.end(), t + 512);
-    }
-    int rc = upload(h, &r.cw, packed);
-    if (rc) return rc;
-    return upload(h, &r.cbias, bias);
-}
-
-// Packs ResNet-50 layer3.1 .. layer3.5's member convs (per block: conv1 1x1 1024 -> 256, conv2 3x3 256 -> 256,
-// conv3 1x1 256 -> 1024 with the residual; BN folded, each + bias + ReLU) into conv_chain_r50.hip's per-wave streams.
-int build_chain_r50(fr_handle* h, StageRec& r) {
-    const int nblk = r.nblk;
-    if ((int)r.conv_ops.size() != 3 * nblk) {
-        set_error("plan: chain_r50 member count");
-        return FR_ERR_ARG;
-    }
-    std::vector<bf16_t> packed(chain_r50_weight_elems(nblk));
-    std::vector<float> bias(chain_r50_bias_floats(nblk), 0.f);
-    for (int blk = 0; blk < nblk; ++blk) {
-        const Op* op[3];
-        const DevConvW* cw[3];
-        std::vector<bf16_t> rows[3];
-        for (int k = 0; k < 3; ++k) {
-            op[k] = &h->ops[r.conv_ops[3 * blk + k]];
-            cw[k] = &h->convw[op[k]->wi];
-            if (cw[k]->w8 || !cw[k]->bias || op[k]->act != 1) {
-                set_error("plan: chain_r50 member conv is not bf16 / f16 + bias + ReLU");
-                return FR_ERR_ARG;
-            }
-            rows[k].resize((size_t)cw[k]->Npad * cw[k]->Kpad);
-            FR_HIP_CHECK(hipMemcpy(rows[k].data(), cw[k]->w, rows[k].size() * sizeof(bf16_t), hipMemcpyDeviceToHost));
-        }
-        const bool shapes = cw[0]->Cout == 256 && cw[0]->K == 1024 && cw[0]->Kh == 1 && cw[0]->Kw == 1 &&
-                            cw[1]->Cout == 256 && cw[1]->K == 2304 && cw[1]->Kh == 3 && cw[1]->Kw == 3 &&
-                            op[1]->sh == 1 && op[1]->ph == 1 && op[1]->pw == 1 &&
-                            cw[2]->Cout == 1024 && cw[2]->K == 256 && cw[2]->Kh == 1 && cw[2]->Kw == 1 &&
-                            op[2]->res >= 0 && op[2]->res_off == 0 && op[0]->res < 0 && op[1]->res < 0;
-        if (!shapes) {
-            set_error("plan: chain_r50 member convs do not have layer3's Bottleneck shapes");
-            return FR_ERR_ARG;
-        }
-        chain_r50_pack_block(rows[0].data(), cw[0]->Kpad, rows[1].data(), cw[1]->Kpad, rows[2].data(), cw[2]->Kpad, blk,
-                             nblk, packed.data());
-        float* t = bias.data() + chain_r50_bias_floats(1) * blk;
-        FR_HIP_CHECK(hipMemcpy(t, cw[0]->bias, 256 * sizeof(float), hipMemcpyDeviceToHost));
-        FR_HIP_CHECK(hipMemcpy(t + 256, cw[1]->bias, 256 * sizeof(float), hipMemcpyDeviceToHost));
-        FR_HIP_CHECK(hipMemcpy(t + 512, cw[2]->bias, 1024 * sizeof(float), hipMemcpyDeviceToHost));
-    }
-    int rc = upload(h, &r.cw, packed);
-    if (rc) return rc;
-    return upload(h, &r.cbias, bias);
-}
-
-// Packs ResNet-50 layer1.1 / layer1.2's member convs (conv1 1x1 256 -> 64, conv2 3x3 64 -> 64, conv3 1x1 64 -> 256
-// with the residual; BN folded, each + bias + ReLU) into conv_bneck28.hip's per-quarter register images.
-int build_bneck28(fr_handle* h, StageRec& r) {
-    const int nblk = r.nblk;
-    if ((int)r.conv_ops.size() != 3 * nblk || (int)r.x_tensors.size() != nblk) {
-        set_error("plan: bneck28 member count");
-        return FR_ERR_ARG;
-    }
-    std::vector<bf16_t> packed(bneck28_block_elems(false) * nblk + (r.bn_ds ? bneck28_block_elems(true) - bneck28_block_elems(false) : 0));
-    std::vector<float> bias((size_t)nblk * 384, 0.f);
-    size_t w_off = 0;
-    for (int blk = 0; blk < nblk; ++blk) {
-        const bool ds = r.bn_ds && blk == 0;
-        const Op* op[3];
-        const DevConvW* cw[3];
-        std::vector<bf16_t> rows[3];
-        for (int k = 0; k < 3; ++k) {
-            op[k] = &h->ops[r.conv_ops[3 * blk + k]];
-            cw[k] = &h->convw[op[k]->wi];
-            if (op[k]->kind != OP_CONV || cw[k]->w8 || !cw[k]->bias || op[k]->act != 1) {
-                set_error("plan: bneck28 member conv is not bf16 / f16 + bias + ReLU");
-                return FR_ERR_ARG;
-            }
-            rows[k].resize((size_t)cw[k]->Npad * cw[k]->Kpad);
-            FR_HIP_CHECK(hipMemcpy(rows[k].data(), cw[k]->w, rows[k].size() * sizeof(bf16_t), hipMemcpyDeviceToHost));
-        }
-        const bool common = cw[0]->Cout == 64 && cw[0]->K == (ds ? 64 : 256) && cw[0]->Kh == 1 && cw[0]->Kw == 1 &&
-                            cw[1]->Cout == 64 && cw[1]->K == 576 && cw[1]->Kh == 3 && cw[1]->Kw == 3 &&
-                            op[1]->sh == 1 && op[1]->ph == 1 && op[1]->pw == 1 && cw[2]->Cout == 256 &&
-                            cw[2]->Kh == 1 && cw[2]->Kw == 1 && op[0]->res < 0 && op[1]->res < 0 && op[0]->in_off == 0;
-        // layer1.0: conv3's K = [t2 64 | maxpool output 64] at stride 1, no residual; 1.1 / 1.2: K 64 + the residual x
-        const bool shapes = common && (ds ? cw[2]->K == 128 && cw[2]->K1 == 64 && cw[2]->C2 == 64 && op[2]->x2 == op[0]->in &&
-                                                op[2]->x2_off == 0 && op[2]->st2 == 1 && op[2]->res < 0
-                                          : cw[2]->K == 64 && op[2]->x2 < 0 && op[2]->res == op[0]->in && op[2]->res_off == 0);
-        if (!shapes) {
-            set_error("plan: bneck28 member convs do not have layer1's Bottleneck shapes");
-            return FR_ERR_ARG;
-        }
-        bneck28_pack_block(rows[0].data(), cw[0]->Kpad, rows[1].data(), cw[1]->Kpad, rows[2].data(), cw[2]->Kpad, ds,
-                           packed.data() + w_off);
-        w_off += bneck28_block_elems(ds);
-        float* t = bias.data() + 384 * blk;
-        FR_HIP_CHECK(hipMemcpy(t, cw[0]->bias, 64 * sizeof(float), hipMemcpyDeviceToHost));
-        FR_HIP_CHECK(hipMemcpy(t + 64, cw[1]->bias, 64 * sizeof(float), hipMemcpyDeviceToHost));
-        FR_HIP_CHECK(hipMemcpy(t + 128, cw[2]->bias, 256 * sizeof(float), hipMemcpyDeviceToHost));
-    }
-    int rc = upload(h, &r.cw, packed);
-    if (rc) return rc;
-    return upload(h, &r.cbias, bias);
-}
-
-// Packs IRV1 repeat_1's member convs (per block: branch1.0 + branch2.0 + branch0 as one 1x1 256 -> 96, branch1.1,
-// branch2.1, branch2.2 3x3 32 -> 32, conv2d 96 -> 256 with the residual) for conv_chain35.hip.
-int build_chain35(fr_handle* h, StageRec& r) {
-    const int nblk = r.nblk;
-    if ((int)r.conv_ops.size() != 5 * nblk || (int)r.x_tensors.size() != nblk) {
-        set_error("plan: chain35 member count");
-        return FR_ERR_ARG;
-    }
-    std::vector<bf16_t> packed(chain35_weight_elems(nblk));
-    std::vector<float> bias(chain35_bias_floats(nblk), 0.f);
-    for (int blk = 0; blk < nblk; ++blk) {
-        const Op* op[5];
-        const DevConvW* cw[5];
-        std::vector<bf16_t> rows[5];
-        std::vector<float> bs[5];
-        for (int k = 0; k < 5; ++k) {
-            op[k] = &h->ops[r.conv_ops[5 * blk + k]];
-            cw[k] = &h->convw[op[k]->wi];
-            if (cw[k]->w8 || !cw[k]->bias || cw[k]->bias9 || op[k]->act != 1) {
-                set_error("plan: chain35 member conv is not bf16 / f16 + bias + ReLU");
-                return FR_ERR_ARG;
-            }
-            rows[k].resize((size_t)cw[k]->Npad * cw[k]->Kpad);
-            FR_HIP_CHECK(hipMemcpy(rows[k].data(), cw[k]->w, rows[k].size() * sizeof(bf16_t), hipMemcpyDeviceToHost));
-            bs[k].resize(cw[k]->Cout);
-            FR_HIP_CHECK(hipMemcpy(bs[k].data(), cw[k]->bias, bs[k].size() * sizeof(float), hipMemcpyDeviceToHost));
-        }
-        bool shapes = cw[0]->Cout == 96 && cw[0]->K == 256 && cw[0]->Kh == 1 && cw[4]->Cout == 256 && cw[4]->K == 96 &&
-                      cw[4]->Kh == 1 && op[4]->res >= 0 && op[4]->res_off == 0;
-        for (int k = 1; k <= 3; ++k)
-            shapes = shapes && cw[k]->Cout == 32 && cw[k]->K == 288 && cw[k]->Kh == 3 && cw[k]->Kw == 3 && op[k]->ph == 1 &&
-                     op[k]->pw == 1 && op[k]->sh == 1 && op[k]->res < 0;
-        if (!shapes) {
-            set_error("plan: chain35 member convs do not have Block35's shapes");
-            return FR_ERR_ARG;
-        }
-        chain35_pack_block(rows[0].data(), cw[0]->Kpad, rows[1].data(), cw[1]->Kpad, rows[2].data(), cw[2]->Kpad,
-                           rows[3].data(), cw[3]->Kpad, rows[4].data(), cw[4]->Kpad, blk, packed.data());
-        chain35_pack_bias(bs[0].data(), bs[1].data(), bs[2].data(), bs[3].data(), bs[4].data(), blk, bias.data());
-    }
-    int rc = upload(h, &r.cw, packed);
-    if (rc) return rc;
-    return upload(h, &r.cbias, bias);
-}
 
 std::string L(int l, int i) { return "layer" + std::to_string(l) + "." + std::to_string(i); }
 
@@ -1031,12 +523,10 @@ void build_iresnet100(Builder& b) {
                 rec.nblk = (int)rec.t_tensors.size();
                 tail_rec = rec;
                 tail_st_op = st_op;
-            } else if (st_op >= 0 && !b.rc) {
+            } else if (st_op >= 0) {
                 rec.out = x;
                 rec.nblk = (int)rec.t_tensors.size();
-                for (int oi : rec.conv_ops) h->ops[oi].stage = h->ops[st_op].stage;
-                b.rc = build_stage(h, rec);
-                h->stages.push_back(rec);
+                b.close_stage(st_op, rec);
             }
             st_op = -1;
         };
@@ -1049,31 +539,21 @@ void build_iresnet100(Builder& b) {
             const bool can = i >= 1 && P == C && !mixed && (f8 ? s14 : (s14 || parts > 0));
             if (st_op >= 0 && (!can || f8 != rec.fp8)) close_stage(false);
             if (can && st_op < 0) {
-                st_op = (int)h->ops.size();
+                st_op = b.open_stage();
                 rec = StageRec{};
+                rec.kind = STAGE_LDS;
                 rec.in = x;
                 rec.parts = s14 ? 1 : parts;
                 rec.H = Ho;
                 rec.C = P;
                 rec.fp8 = f8;
-                Op op;
-                op.kind = OP_STAGE;
-                op.stage = (int)h->stages.size();
-                h->ops.push_back(op);
             }
             const int Hin = i == 0 ? H : Ho, st = i == 0 ? 2 : 1;
             const bool fuse = i == 0 && b.fuse_ds(P, C, pre);
             // layer1.0 as one fused launch (conv_trans.hip) beside its member convs (measured per batch size)
             const bool tr = i == 0 && fuse && !b.is_fp8(pre + ".conv1") && !b.is_fp8(pre + ".conv2") &&
                             trans_supported(1, H, H, C, P, P, 9 * C, 9 * P + C);
-            int tr_op = -1;
-            if (tr) {
-                tr_op = (int)h->ops.size();
-                Op op;
-                op.kind = OP_STAGE;
-                op.stage = (int)h->stages.size();
-                h->ops.push_back(op);
-            }
+            const int tr_op = tr ? b.open_stage() : -1;
             const int hmid = b.tensor(Hin, Hin, P, pre + ".prelu");
             b.conv({pre + ".conv1"}, x, 0, C, hmid, 0, 3, 3, 1, 1, 1, 1, 2);
             if (tail_st_op >= 0 && !b.rc) {  // layer4.0.conv1: the layer3 stage's tail when it fits, then close it
@@ -1087,11 +567,8 @@ void build_iresnet100(Builder& b) {
                     op.pw == 1 && op.in == tail_rec.out && op.in_off == 0 && op.out_off == 0 && op.res < 0 && op.x2 < 0 &&
                     op.out2 < 0 && h->tensors[hmid].C == 2 * TC && !h->tensors[hmid].f16)
                     tail_rec.tail_op = oi;
-                for (int oj : tail_rec.conv_ops) h->ops[oj].stage = h->ops[tail_st_op].stage;
-                if (tail_rec.tail_op >= 0) h->ops[oi].stage = h->ops[tail_st_op].stage;
-                b.rc = build_stage(h, tail_rec);
-                if (tail_rec.tail_op >= 0) tail_rec.conv_ops.push_back(oi);
-                h->stages.push_back(tail_rec);
+                if (tail_rec.tail_op >= 0) tail_rec.conv_ops.push_back(oi);  // (the packer reads the blocks' 2 * nblk first)
+                b.close_stage(tail_st_op, tail_rec);
                 tail_st_op = -1;
             }
             int res = x;
@@ -1107,14 +584,12 @@ void build_iresnet100(Builder& b) {
                 b.conv({pre + ".conv2"}, hmid, 0, P, y, 0, 3, 3, st, st, 1, 1, 0, res, 0);
             if (tr && !b.rc) {
                 StageRec t;
-                t.trans = true;
+                t.kind = STAGE_TRANS;
                 t.in = x; t.out = y; t.nblk = 1; t.H = H; t.C = P;
                 t.conv_ops = {(int)h->ops.size() - 2, (int)h->ops.size() - 1};
                 t.t_tensors = {hmid};
                 t.x_tensors = {y};
-                for (int oi : t.conv_ops) h->ops[oi].stage = h->ops[tr_op].stage;
-                b.rc = build_trans(h, t);
-                h->stages.push_back(t);
+                b.close_stage(tr_op, t);
             }
             if (st_op >= 0 && !b.rc) {
                 rec.conv_ops.push_back((int)h->ops.size() - 2);
@@ -1212,20 +687,14 @@ void build_resnet50(Builder& b) {
     const int c1 = b.tensor(56, 56, 64, "backbone.relu");
     // conv1 + maxpool are also emitted as one launch (conv_stem_r50.hip) beside the member ops
     const bool st = h->dtype != FR_DTYPE_FP8;
-    const int st_op = (int)h->ops.size();
-    if (st) {
-        Op op;
-        op.kind = OP_STAGE;
-        op.stage = (int)h->stages.size();
-        h->ops.push_back(op);
-    }
+    const int st_op = st ? b.open_stage() : -1;
     b.stem = true;
     b.conv({"backbone.conv1"}, in, 0, 8, c1, 0, 7, 7, 2, 2, 3, 3, 1);
     int x = b.tensor(28, 28, 64, "backbone.maxpool");
     b.maxpool(c1, x, 0, 3, 2, 1);
     if (st && !b.rc) {
         StageRec sr;
-        sr.chain = 56;
+        sr.kind = STAGE_STEM_R50;
         sr.in = in; sr.out = x; sr.H = 112; sr.C = 8; sr.nblk = 1;
         sr.conv_ops = {st_op + 1, st_op + 2};
         const Op& cv = h->ops[st_op + 1];
@@ -1234,10 +703,8 @@ void build_resnet50(Builder& b) {
             cv.sh != 2 || cv.ph != 3 || cv.res >= 0 || h->ops[st_op + 2].kind != OP_MAXPOOL) {
             set_error("plan: ResNet-50 stem does not have the fused kernel's shape");
             b.rc = FR_ERR_ARG;
-        } else {
-            for (int oi : sr.conv_ops) h->ops[oi].stage = h->ops[st_op].stage;
-            h->stages.push_back(sr);
         }
+        b.close_stage(st_op, sr);
     }
     const int planes[4] = {64, 128, 256, 512}, nblk[4] = {3, 4, 6, 3}, strd[4] = {1, 2, 2, 2};
     int H = 28, C = 64;
@@ -1253,22 +720,14 @@ void build_resnet50(Builder& b) {
             // into conv3 (fuse_ds), else from layer1.1
             const bool bn_ds = i == 0 && C == P && b.fuse_ds(P, C, pre);
             if (l == 0 && bn_op < 0 && (bn_ds || i == 1) && h->dtype != FR_DTYPE_FP8 && bneck28_supported(H, H, 4 * P, P)) {
-                bn_op = (int)h->ops.size();
-                Op op;
-                op.kind = OP_STAGE;
-                op.stage = (int)h->stages.size();
-                h->ops.push_back(op);
-                bn.chain = 28;
+                bn_op = b.open_stage();
+                bn.kind = STAGE_BNECK28;
                 bn.bn_ds = bn_ds;
                 bn.in = x; bn.H = H; bn.C = C; bn.nblk = nblk[l] - i;
             }
             if (l == 2 && i == 1 && h->dtype != FR_DTYPE_FP8 && H == 7 && chain_r50_supported(H, H, C, nblk[l] - 1)) {
-                ch_op = (int)h->ops.size();
-                Op op;
-                op.kind = OP_STAGE;
-                op.stage = (int)h->stages.size();
-                h->ops.push_back(op);
-                ch.chain = 50;
+                ch_op = b.open_stage();
+                ch.kind = STAGE_CHAIN_R50;
                 ch.in = x; ch.H = H; ch.C = C; ch.nblk = nblk[l] - 1;
             }
             const size_t op0 = h->ops.size();
@@ -1299,17 +758,13 @@ void build_resnet50(Builder& b) {
             C = 4 * P;
             H = Ho;
         }
-        if (bn_op >= 0 && l == 0 && !b.rc) {
+        if (bn_op >= 0 && l == 0) {
             bn.out = x;
-            for (int oi : bn.conv_ops) h->ops[oi].stage = h->ops[bn_op].stage;
-            b.rc = build_bneck28(h, bn);
-            h->stages.push_back(bn);
+            b.close_stage(bn_op, bn);
         }
-        if (ch_op >= 0 && l == 2 && !b.rc) {
+        if (ch_op >= 0 && l == 2) {
             ch.out = x;
-            for (int oi : ch.conv_ops) h->ops[oi].stage = h->ops[ch_op].stage;
-            b.rc = build_chain_r50(h, ch);
-            h->stages.push_back(ch);
+            b.close_stage(ch_op, ch);
         }
     }
     const int pool = b.tensor(1, 1, C, "backbone.avgpool");
@@ -1352,14 +807,7 @@ void build_irv1(Builder& b) {
     if (mid16) h->tensors[x].f16 = true;
     b.stem = true;
     // conv2d_1a .. conv2d_3b also as one launch (conv_stem160.hip) beside the member ops, measured per batch size
-    int st_op = -1;
-    if (h->dtype != FR_DTYPE_FP8) {
-        st_op = (int)h->ops.size();
-        Op op;
-        op.kind = OP_STAGE;
-        op.stage = (int)h->stages.size();
-        h->ops.push_back(op);
-    }
+    const int st_op = h->dtype != FR_DTYPE_FP8 ? b.open_stage() : -1;
     b.conv({m + "conv2d_1a"}, in, 0, 8, a, 0, 3, 3, 2, 2, 0, 0, 1);
     b.conv({m + "conv2d_2a"}, a, 0, 32, bb, 0, 3, 3, 1, 1, 0, 0, 1);
     b.conv({m + "conv2d_2b"}, bb, 0, 32, c, 0, 3, 3, 1, 1, 1, 1, 1);
@@ -1367,8 +815,8 @@ void build_irv1(Builder& b) {
     b.conv({m + "conv2d_3b"}, d, 0, 64, e, 0, 1, 1, 1, 1, 0, 0, 1);
     if (st_op >= 0 && !b.rc) {
         StageRec sr;
-        sr.stem = true;
-        sr.in = in; sr.out = e; sr.H = 160; sr.C = 80;
+        sr.kind = STAGE_STEM160;
+        sr.in = in; sr.out = e; sr.H = 160; sr.C = 80; sr.nblk = 1;
         const int n = (int)h->ops.size();
         sr.conv_ops = {n - 5, n - 4, n - 3, n - 2, n - 1};
         const Op& o1 = h->ops[n - 5];
@@ -1382,14 +830,7 @@ void build_irv1(Builder& b) {
         bool ok = stem160_supported(160, 160, 8, c1.K, c2.K, c3.K, c4.K, c1.Cout, c2.Cout, c3.Cout, c4.Cout) &&
                   h->tensors[in].f16 == h->tensors[e].f16 && o1.act == 1 && o2.act == 1 && o3.act == 1 && o4.act == 1;
         for (const DevConvW* cw : {&c1, &c2, &c3, &c4}) ok = ok && cw->bias && !cw->bias9 && !cw->w8;
-        if (ok) {
-            for (int oi : sr.conv_ops) h->ops[oi].stage = h->ops[st_op].stage;
-            h->stages.push_back(sr);
-        } else {
-            h->ops.erase(h->ops.begin() + st_op);  // no fused stem for these weights: the member ops only
-            for (auto& op : h->ops)
-                if (op.kind == OP_STAGE && op.stage >= (int)h->stages.size()) --op.stage;
-        }
+        b.close_stage(st_op, sr, ok);  // not ok: no fused stem for these weights, the member ops only
     }
     b.conv({m + "conv2d_4a"}, e, 0, 80, f, 0, 3, 3, 1, 1, 0, 0, 1);
     b.conv({m + "conv2d_4b"}, f, 0, 192, x, 0, 3, 3, 2, 2, 0, 0, 1);
@@ -1398,12 +839,8 @@ void build_irv1(Builder& b) {
     int c35_op = -1;
     StageRec c35;
     if (h->dtype != FR_DTYPE_FP8 && chain35_supported(17, 17, 256, 5)) {
-        c35_op = (int)h->ops.size();
-        Op op;
-        op.kind = OP_STAGE;
-        op.stage = (int)h->stages.size();
-        h->ops.push_back(op);
-        c35.chain = 35;
+        c35_op = b.open_stage();
+        c35.kind = STAGE_CHAIN35;
         c35.in = x; c35.H = 17; c35.C = 256; c35.nblk = 5;
     }
     for (int i = 0; i < 5; ++i) {
@@ -1425,11 +862,9 @@ void build_irv1(Builder& b) {
         }
         x = y;
     }
-    if (c35_op >= 0 && !b.rc) {
+    if (c35_op >= 0) {
         c35.out = x;
-        for (int oi : c35.conv_ops) h->ops[oi].stage = h->ops[c35_op].stage;
-        b.rc = build_chain35(h, c35);
-        h->stages.push_back(c35);
+        b.close_stage(c35_op, c35);
     }
     {  // mixed_6a
         const std::string p = m + "mixed_6a.";
@@ -1449,12 +884,8 @@ void build_irv1(Builder& b) {
     int ch_op = -1;
     StageRec ch;
     if (h->dtype != FR_DTYPE_FP8 && chain17_supported(8, 8, 896, 10)) {
-        ch_op = (int)h->ops.size();
-        Op op;
-        op.kind = OP_STAGE;
-        op.stage = (int)h->stages.size();
-        h->ops.push_back(op);
-        ch.chain = 17;
+        ch_op = b.open_stage();
+        ch.kind = STAGE_CHAIN17;
         ch.in = x; ch.H = 8; ch.C = 896; ch.nblk = 10;
     }
     for (int i = 0; i < 10; ++i) {
@@ -1471,11 +902,9 @@ void build_irv1(Builder& b) {
             for (int k = 4; k >= 1; --k) ch.conv_ops.push_back((int)h->ops.size() - k);
         x = y;
     }
-    if (ch_op >= 0 && !b.rc) {
+    if (ch_op >= 0) {
         ch.out = x;
-        for (int oi : ch.conv_ops) h->ops[oi].stage = h->ops[ch_op].stage;
-        b.rc = build_chain17(h, ch);
-        h->stages.push_back(ch);
+        b.close_stage(ch_op, ch);
     }
     {  // mixed_7a
         const std::string p = m + "mixed_7a.";
@@ -1613,54 +1042,6 @@ bool band_enabled() {
     static const bool on = [] { return !ab_int("no_band", 0); }();
     return on;
 }
-
-hipEvent_t prof_event(fr_handle* h) {
-    if (!h->ev_free.empty()) { hipEvent_t e = h->ev_free.back(); h->ev_free.pop_back(); return e; }
-    hipEvent_t e = nullptr;
-    if (hipEventCreate(&e) != hipSuccess) return nullptr;
-    return e;
-}
-
-// Brackets one launch with two events when profiling is on; `cls` names the kernel instantiation so
-// the totals line up with rocprofv3's per-kernel rows.
-struct ProfScope {
-    fr_handle* h; hipStream_t s; hipEvent_t a = nullptr, b = nullptr; bool stamped = false;
-    std::string cls; double flops = 0, bytes = 0;  // algorithmic FLOPs and HBM bytes of the launch
-    ProfScope(fr_handle* h_, hipStream_t s_) : h(h_), s(s_) {}
-    // Call right before the launch once the class is known.  With `ka` the pair is handed to the
-    // conv launcher, which stamps it from the dispatch packet (hipExtLaunchKernel: no extra stream
-    // commands); otherwise the pair is recorded around the launch(es) with hipEventRecord.
-    bool slot_pair = false;
-    void start(const std::string& c, ConvArgs* ka = nullptr) {
-        cls = c;
-        if (!h->prof && h->slot >= 0 && cls == h->slot_class) {  // graph-slot timing
-            const int ord = h->slot_seen++;
-            if (h->slot_seen > h->slot_nl) h->slot_nl = h->slot_seen;
-            if (!h->slot_done && ord == h->slot % h->slot_nl) {
-                (void)hipEventRecord(h->slot_events[h->slot].first, s);
-                h->slot_done = true;
-                slot_pair = true;
-            }
-            return;
-        }
-        if (!h->prof || (!h->prof_only.empty() && h->prof_only != cls)) return;
-        if (h->prof_seen++ % h->prof_stride != 0) return;
-        a = prof_event(h);
-        b = a ? prof_event(h) : nullptr;
-        if (!b) { if (a) h->ev_free.push_back(a); a = nullptr; return; }
-        if (ka) { ka->ev0 = a; ka->ev1 = b; stamped = true; }
-        else (void)hipEventRecord(a, s);
-    }
-    ~ProfScope() {
-        if (slot_pair) {
-            (void)hipEventRecord(h->slot_events[h->slot].second, s);
-            h->slot_work[h->slot] = {flops, bytes};
-        }
-        if (!a) return;
-        if (!stamped) (void)hipEventRecord(b, s);
-        h->prof_pending.push_back({cls, a, b, flops, bytes});
-    }
-};
 
 double conv_flops(const ConvArgs& a) { return 2.0 * (double)a.M * a.Cout * ((double)a.Cin * a.Kh * a.Kw + (a.x2 ? a.C2 : 0)); }
 
@@ -1983,80 +1364,6 @@ int run_conv_args(fr_handle* h, ConvArgs& a, hipStream_t s) {
     return FR_OK;
 }
 
-// Whether the LDS-resident stage kernel runs at batch B.  It puts one image on one CU.  Up to one image
-// per CU it beats the per-conv launches at every batch size (tools/batch_sweep.py, profiles/
-// r02_batch_sweep.jsonl: B = 1 3.76 vs 3.88 ms, B = 128 5.39 vs 5.73 ms): a small batch leaves CUs idle
-// either way, since per-conv grids of B*196 positions are a handful of tiles.  Above one round a last
-// round that is mostly empty costs a whole stage time, so auto mode then requires the rounds to be at
-// least stage_min_fill % full (B = 512: 100 %, B = 257: 50 % -> per-conv).
-// A split stage puts one image on `parts` CUs: a round is n_cu / parts images.  FR_AB no_split_stage /
-// =28 / =56 turns the split stages off (all / layer2 / layer1) for A/B timing.
-static bool split_stage_enabled(int H) {
-    static const int off = [] { return ab_int("no_split_stage", 0); }();
-    return !(off == 1 || off == H);
-}
-
-static int stage_choice(const fr_handle* h, int st, int B);
-
-// FR_AB no_trans: IResNet100 layer1.0 always runs as its two member convs (A/B timing)
-static bool trans_enabled() {
-    static const bool on = [] { return !ab_int("no_trans", 0); }();
-    return on;
-}
-
-// FR_AB no_chain: IRV1 repeat_1 / repeat_2 and ResNet-50's stem / layer1 / layer3 always run as their member ops
-// (A/B timing); no_chain17 / no_chain35 / no_chain50 / no_bneck28 / no_stem_r50: only that one
-static bool chain_enabled(int kind) {
-    static const bool all = !ab_int("no_chain", 0), c17 = !ab_int("no_chain17", 0), c35 = !ab_int("no_chain35", 0),
-                      c50 = !ab_int("no_chain50", 0), c28 = !ab_int("no_bneck28", 0), c56 = !ab_int("no_stem_r50", 0);
-    return all && (kind == 17 ? c17 : kind == 35 ? c35 : kind == 28 ? c28 : kind == 56 ? c56 : c50);
-}
-
-// FR_AB no_stem160: the IRV1 stem always runs as its member ops (A/B timing)
-static bool ab_stem160() {
-    static const bool on = [] { return !ab_int("no_stem160", 0); }();
-    return on;
-}
-
-static bool stage_runs(const fr_handle* h, int B, const StageRec& r, int st) {
-    if (h->stage_mode == 0 || h->invariant) return false;
-    const int kind_bit = r.stem ? 2 : r.chain == 35 ? 4 : r.chain == 50 ? 16 : r.chain == 28 ? 32 : r.chain == 56 ? 64
-                       : r.chain ? 8 : 1;
-    if (!(h->fused_mask & kind_bit)) return false;
-    // the fused transition keeps no t tensor and records no amax
-    if (r.trans && (h->keep_inter || (h->amax && h->need_amax[r.out]) || !trans_enabled())) return false;
-    if (r.parts > 1 && (h->no_split || !split_stage_enabled(r.H))) return false;
-    if (r.chain && (h->keep_inter || !chain_enabled(r.chain))) return false;  // no intermediates; FR_AB no_chain
-    if (r.stem && (h->keep_inter || !ab_stem160())) return false;         // FR_AB no_stem160
-    if (h->stage_mode == 1) {  // measured at this batch size (measure_stage)
-        const int c = stage_choice(h, st, B);
-        if (c >= 0) return c == 1;
-    }
-    const int cap = std::max(1, h->n_cu / r.parts);
-    if (h->stage_mode == 2 || B <= cap) return true;
-    const int64_t rounds = (B + cap - 1) / cap;
-    return (int64_t)B * 100 >= (int64_t)h->stage_min_fill * rounds * cap;
-}
-
-// Per-op skip rule: a stage op runs when its plan entry says so; its member convs run when it does not (Op::grp).
-static std::vector<char> stage_plan(const fr_handle* h, int B) {
-    std::vector<char> run(h->stages.size());
-    for (size_t i = 0; i < h->stages.size(); ++i) run[i] = stage_runs(h, B, h->stages[i], (int)i);
-    return run;
-}
-
-static bool op_skipped(const Op& op, const std::vector<char>& run) {
-    if (op.kind == OP_STAGE) return !run[op.grp];
-    return op.grp >= 0 && run[op.grp];
-}
-
-// Whether a forward at batch B runs a split stage (its parts wait for each other).
-static bool split_runs(const fr_handle* h, int B) {
-    for (size_t i = 0; i < h->stages.size(); ++i)
-        if (h->stages[i].parts > 1 && stage_runs(h, B, h->stages[i], (int)i)) return true;
-    return false;
-}
-
 // Co-residency of a split stage's parts holds while the stage kernel is the only long-running kernel
 // on the device.  Two split-stage forwards of different handles on one device could
 // each hold CUs the other's parts need, so the forwards of handles that share a device (in this
@@ -2144,10 +1451,10 @@ static bool ms_enabled() {
     return e && e[0] == '1';
 }
 
-// One LDS-resident stage launch (+ the amax pass an e4m3 reader of its output needs).
-static int run_conv_op(fr_handle* h, const Op& op, int B, int f16, hipStream_t s);
+}  // namespace
 
-static int run_maxpool_op(fr_handle* h, const Op& op, int B, int f16, hipStream_t s) {
+// (shared with stages.cpp: a stage's member ops run beside it when it is measured)
+int fr::run_maxpool_op(fr_handle* h, const Op& op, int B, int f16, hipStream_t s) {
     ProfScope ps(h, s);
     ps.start("maxpool");
     const auto& ti = h->tensors[op.in];
@@ -2161,181 +1468,8 @@ static int run_maxpool_op(fr_handle* h, const Op& op, int B, int f16, hipStream_
     return FR_OK;
 }
 
-static int run_stage(fr_handle* h, const Op& op, int B, int f16, const std::vector<char>& stage_run, hipStream_t s) {
-    const StageRec& r = h->stages[op.stage];
-    if (r.stem) {
-        const DevConvW* cw[4];
-        for (int k = 0, j = 0; k < 5; ++k)
-            if (h->ops[r.conv_ops[k]].kind == OP_CONV) cw[j++] = &h->convw[h->ops[r.conv_ops[k]].wi];
-        Stem160Args a{};
-        a.x = h->tensors[r.in].dev;
-        a.u8 = h->fwd_u8;  // the crops when the forward skipped the preparation op (forward, OP_PRE)
-        a.y = h->tensors[r.out].dev;
-        a.w1 = cw[0]->w; a.w2 = cw[1]->w; a.w3 = cw[2]->w; a.w4 = cw[3]->w;
-        a.b1 = cw[0]->bias; a.b2 = cw[1]->bias; a.b3 = cw[2]->bias; a.b4 = cw[3]->bias;
-        a.kp1 = cw[0]->Kpad; a.kp2 = cw[1]->Kpad; a.kp3 = cw[2]->Kpad; a.kp4 = cw[3]->Kpad;
-        a.B = B; a.f16 = f16 || h->tensors[r.in].f16;
-        ProfScope ps(h, s);
-        ps.flops = 2.0 * B * (79.0 * 79 * 32 * 72 + 77.0 * 77 * 32 * 288 + 77.0 * 77 * 64 * 288 + 38.0 * 38 * 80 * 64);
-        ps.bytes = (double)B * ((a.u8 ? 3.0 : 16.0) * 160 * 160 + 2.0 * 38 * 38 * 80);
-        ps.start("stem160");
-        FR_HIP_CHECK(launch_stem160(a, s));
-        return FR_OK;
-    }
-    if (r.chain == 35) {
-        Chain35Args c{};
-        c.io[0] = h->tensors[r.in].dev;
-        for (int i = 0; i < r.nblk; ++i) c.io[i + 1] = h->tensors[r.x_tensors[i]].dev;
-        c.w = r.cw; c.bias = r.cbias; c.B = B; c.nblk = r.nblk; c.f16 = f16 || h->tensors[r.in].f16;
-        ProfScope ps(h, s);
-        // per block and pixel: 256 x 96 + 3 x 288 x 32 + 96 x 256 = 76,800 MACs
-        ps.flops = 2.0 * B * 289.0 * 76800.0 * r.nblk;
-        ps.bytes = 2.0 * 2.0 * B * 289.0 * 256.0 + 2.0 * 76800.0 * r.nblk;
-        ps.start("chain block35");
-        FR_HIP_CHECK(launch_chain35(c, s));
-        return FR_OK;
-    }
-    if (r.chain == 56) {
-        const Op& cv = h->ops[r.conv_ops[0]];
-        const DevConvW& cw = h->convw[cv.wi];
-        StemR50Args a{};
-        a.x = h->tensors[r.in].dev;
-        a.u8 = h->fwd_u8;  // the crops when the forward skipped the preparation op (forward, OP_PRE)
-        a.y = h->tensors[r.out].dev;
-        a.w = cw.w; a.bias = cw.bias; a.Kpad = cw.Kpad; a.B = B; a.f16 = f16 || h->tensors[r.in].f16;
-        ProfScope ps(h, s);
-        ps.flops = 2.0 * B * 3136.0 * 64.0 * 392.0;
-        ps.bytes = (double)B * (112.0 * 112 * (a.u8 ? 3.0 : 16.0) + 28.0 * 28 * 64 * 2);
-        ps.start("stem r50");
-        FR_HIP_CHECK(launch_stem_r50(a, s));
-        return FR_OK;
-    }
-    if (r.chain == 28) {
-        Chain17Args c{};
-        c.B = B; c.nblk = 1; c.f16 = f16;
-        size_t w_off = 0;
-        for (int i = 0; i < r.nblk; ++i) {
-            const bool ds = r.bn_ds && i == 0;
-            c.x = h->tensors[i ? r.x_tensors[i - 1] : r.in].dev;
-            c.y = h->tensors[r.x_tensors[i]].dev;
-            c.w = r.cw + w_off;
-            c.bias = r.cbias + 384 * i;
-            w_off += bneck28_block_elems(ds);
-            ProfScope ps(h, s);
-            // per pixel: 256 x 64 + 576 x 64 + 64 x 256 = 69,632 MACs (layer1.0: 64 x 64 + 576 x 64 + 128 x 256 = 73,728)
-            const double macs = ds ? 73728.0 : 69632.0;
-            ps.flops = 2.0 * B * 784.0 * macs;
-            ps.bytes = 2.0 * B * 784.0 * ((ds ? 64.0 : 256.0) + 256.0) + 2.0 * macs;
-            ps.start(ds ? "bneck28 layer1.0" : "bneck28 layer1");
-            FR_HIP_CHECK(launch_bneck28(c, ds, s));
-        }
-        return FR_OK;
-    }
-    if (r.chain == 50) {
-        Chain17Args c{};
-        c.x = h->tensors[r.in].dev;
-        c.y = h->tensors[r.out].dev;
-        c.w = r.cw; c.bias = r.cbias; c.B = B; c.nblk = r.nblk; c.f16 = f16;
-        ProfScope ps(h, s);
-        // per block and pixel: 1024 x 256 + 2304 x 256 + 256 x 1024 = 1,114,112 MACs
-        ps.flops = 2.0 * B * 49.0 * 1114112.0 * r.nblk;
-        ps.bytes = 2.0 * 2.0 * B * 49.0 * 1024.0 + 2.0 * 1114112.0 * r.nblk;
-        ps.start("chain r50 layer3");
-        FR_HIP_CHECK(launch_chain_r50(c, s));
-        return FR_OK;
-    }
-    if (r.chain) {
-        Chain17Args c{};
-        c.x = h->tensors[r.in].dev;
-        c.y = h->tensors[r.out].dev;
-        c.w = r.cw; c.bias = r.cbias; c.B = B; c.nblk = r.nblk; c.f16 = f16 || h->tensors[r.in].f16;
-        ProfScope ps(h, s);
-        // per block and pixel: 896 x 256 (branch1.0 + branch0) + 2 x 896 x 128 (1x7, 7x1) + 256 x 896 MACs
-        ps.flops = 2.0 * B * 64.0 * 688128.0 * r.nblk;
-        ps.bytes = 2.0 * 2.0 * B * 64.0 * 896.0 + 2.0 * 688128.0 * r.nblk;
-        ps.start("chain block17");
-        FR_HIP_CHECK(launch_chain17(c, s));
-        return FR_OK;
-    }
-    if (r.trans) {
-        TransArgs t{};
-        t.x = h->tensors[r.in].dev;
-        t.y = h->tensors[r.out].dev;
-        t.w1 = r.tw1; t.w2 = r.tw2; t.ep1 = r.tep1; t.slope1 = r.tsl1; t.b2 = r.tb2;
-        t.B = B; t.f16 = f16;
-        ProfScope ps(h, s);
-        // conv1 (B x 112^2 x 64 x 576) + conv2 with the downsample (B x 56^2 x 64 x 640)
-        ps.flops = 2.0 * B * (12544.0 * 64 * 576 + 3136.0 * 64 * 640);
-        ps.bytes = 2.0 * B * (12544.0 + 3136.0) * 64 + 2.0 * 64 * (576 + 640);
-        ps.start("trans layer1.0");
-        FR_HIP_CHECK(launch_trans(t, s));
-        return FR_OK;
-    }
-    StageArgs a{};
-    a.x = h->tensors[r.in].dev;
-    a.y = h->tensors[r.out].dev;
-    a.w = r.w;
-    a.conv = r.table;
-    a.ep = r.ep;
-    a.slope = r.slope;
-    if (h->keep_inter) { a.dbg_x = r.dbg; a.dbg_t = r.dbg + r.nblk; }
-    a.B = B;
-    a.nblk = r.nblk;
-    a.f16 = f16;
-    a.xchg = h->stage_xchg;
-    a.flags = h->stage_flags + (size_t)h->max_batch * 4 * op.stage;  // the stage's own counter region
-    a.spin_timeouts = h->stage_spin;
-    a.fail_host = h->fail_dev;
-    a.spin_limit = h->spin_limit;
-    a.variant = h->stage_variant;
-    // the tail conv runs inside the stage kernel, except under the legacy 14-fragment kernel (variant 1), which
-    // has no tail: there it runs as its own conv after the stage
-    const bool tail_in = r.tail_op >= 0 && (r.parts > 1 || a.variant != 1);
-    if (tail_in) {
-        a.ntail = 2;
-        a.y2 = h->tensors[h->ops[r.tail_op].out].dev;
-    }
-    {
-        ProfScope ps(h, s);
-        ps.flops = 2.0 * r.nblk * 2.0 * B * r.H * r.H * (double)r.C * 9.0 * r.C;
-        ps.bytes = 2.0 * B * r.H * r.H * (double)r.C * 2.0 + 2.0 * r.nblk * 9.0 * r.C * r.C * (r.fp8 ? 1.0 : 2.0);
-        if (tail_in) {  // + the tail conv: 3x3 C -> 2C at H x H, its 2C-channel output and weights
-            ps.flops += 2.0 * B * r.H * r.H * 2.0 * r.C * 9.0 * r.C;
-            ps.bytes += 2.0 * B * r.H * r.H * 2.0 * r.C + 2.0 * 9.0 * r.C * 2.0 * r.C;
-        }
-        if (r.fp8) {
-            a.w = (const bf16_t*)r.w8;
-            a.wscale = r.wscale;
-            ps.start("stage8 layer3");
-            FR_HIP_CHECK(launch_stage8(a, s));
-        } else {
-            ps.start(r.H == 14 ? "stage layer3" : (r.H == 28 ? "stage layer2" : "stage layer1"));
-            FR_HIP_CHECK(r.parts > 1 ? launch_split_stage(a, r.H, r.C, s) : launch_stage(a, s));
-        }
-    }
-    if (r.tail_op >= 0 && !tail_in) {
-        const int rc = run_conv_op(h, h->ops[r.tail_op], B, f16, s);
-        if (rc) return rc;
-    }
-    // the stages have no amax epilogue: when a per-conv e4m3 conv reads the stage output (e.g.
-    // layer4.0 under FR_FP8_PLAN=all), its activation scale comes from one reduction pass here
-    if (h->amax && h->need_amax[r.out] &&
-        std::any_of(h->ops.begin(), h->ops.end(), [&](const Op& c) {  // a per-conv e4m3 reader runs
-            return c.kind == OP_CONV && c.in == r.out && c.in_off == 0 && c.wi >= 0 && h->convw[c.wi].w8 &&
-                   !op_skipped(c, stage_run);
-        })) {
-        const auto& t = h->tensors[r.out];
-        ProfScope pa(h, s);
-        pa.bytes = 2.0 * B * t.H * t.W * t.C;
-        pa.start("amax");
-        FR_HIP_CHECK(launch_amax(t.dev, (size_t)B * t.H * t.W * t.C, f16 || t.f16,
-                                 h->amax + (size_t)r.out * FR_AMAX_SLOTS, FR_AMAX_SLOTS, s));
-    }
-    return FR_OK;
-}
-
 // One conv op: its ConvArgs from the plan's tensors and weights, then the kernel choice (run_conv_args).
-static int run_conv_op(fr_handle* h, const Op& op, int B, int f16, hipStream_t s) {
+int fr::run_conv_op(fr_handle* h, const Op& op, int B, int f16, hipStream_t s) {
     const auto& cw = h->convw[op.wi];
     const auto& ti = h->tensors[op.in];
     const auto& to = h->tensors[op.out];
@@ -2374,52 +1508,7 @@ static int run_conv_op(fr_handle* h, const Op& op, int B, int f16, hipStream_t s
     return run_conv_args(h, a, s);
 }
 
-// Stage or per-conv launches for a stage's blocks at batch B, measured (FR_OPT_STAGE = 1, the default): in the
-// eager tuning forward of a new batch size the member convs run (and tune their kernels), then the member
-// sequence and the stage are timed with HIP events, and the faster is kept for B (-1: not measured yet).  The
-// winner runs last, so the tuning forward's output equals every later forward's.
-static int stage_choice(const fr_handle* h, int st, int B) {
-    for (const auto& m : h->stage_meas)
-        if (m.stage == st && m.B == B) return m.run;
-    return -1;
-}
-
-static int measure_stage(fr_handle* h, const Op& op, int B, int f16, const std::vector<char>& stage_run, hipStream_t s) {
-    const std::vector<int>& mem = h->stages[op.stage].conv_ops;
-    auto fused = [&]() { return run_stage(h, op, B, f16, stage_run, s); };
-    auto members = [&]() {
-        for (int oi : mem) {
-            const Op& mo = h->ops[oi];
-            const int rc = mo.kind == OP_MAXPOOL ? run_maxpool_op(h, mo, B, f16, s) : run_conv_op(h, mo, B, f16, s);
-            if (rc) return rc;
-        }
-        return (int)FR_OK;
-    };
-    int rc = members();  // tunes the member convs' kernels
-    if (!rc) rc = fused();  // warm
-    if (rc) return rc;
-    hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
-    for (auto& e : ev) FR_HIP_CHECK(hipEventCreate(&e));
-    float t_conv = 1e30f, t_stage = 1e30f;
-    for (int pass = 0; pass < 2 && !rc; ++pass) {  // best of two, interleaved
-        FR_HIP_CHECK(hipEventRecord(ev[0], s));
-        rc = members();
-        FR_HIP_CHECK(hipEventRecord(ev[1], s));
-        if (!rc) rc = fused();
-        FR_HIP_CHECK(hipEventRecord(ev[2], s));
-        FR_HIP_CHECK(hipEventSynchronize(ev[2]));
-        float a = 0.f, b = 0.f;
-        FR_HIP_CHECK(hipEventElapsedTime(&a, ev[0], ev[1]));
-        FR_HIP_CHECK(hipEventElapsedTime(&b, ev[1], ev[2]));
-        t_conv = std::min(t_conv, a);
-        t_stage = std::min(t_stage, b);
-    }
-    for (auto& e : ev) (void)hipEventDestroy(e);
-    if (rc) return rc;
-    const int run = t_stage <= t_conv ? 1 : 0;
-    h->stage_meas.push_back({op.grp, B, run, t_stage, t_conv});
-    return run ? FR_OK : members();  // the stage's output is in place; else the per-conv one replaces it
-}
+namespace {
 
 int forward(fr_handle* h, const void* in, int in_fmt, int B, float* out, int flags, hipStream_t s_main) {
     const int f16 = h->dtype == FR_DTYPE_F16;
@@ -2504,7 +1593,7 @@ int forward(fr_handle* h, const void* in, int in_fmt, int B, float* out, int fla
             case OP_PRE: {
                 h->fwd_u8 = nullptr;
                 if (in_fmt == FR_IN_U8_NHWC && oi + 1 < h->ops.size() && h->ops[oi + 1].kind == OP_STAGE &&
-                    (h->stages[h->ops[oi + 1].stage].stem || h->stages[h->ops[oi + 1].stage].chain == 56) &&
+                    stage_takes_u8(h->stages[h->ops[oi + 1].stage]) &&
                     !op_skipped(h->ops[oi + 1], stage_run) &&
                     !(h->tuning && h->stage_mode == 1 && !h->keep_inter && !h->prof &&
                       stage_choice(h, h->ops[oi + 1].grp, B) < 0)) {
@@ -3148,71 +2237,14 @@ int fr_segment_mean_normalize(const float* E, int D, const int32_t* seg_start, i
     return FR_OK;
 }
 
-// " <fused ms> <per-conv ms>" of a stage measured at batch B (measure_stage), else ""
-static std::string meas_note(const fr_handle* h, int grp, int B) {
-    for (const auto& m : h->stage_meas)
-        if (m.stage == grp && m.B == B) {
-            char t[64];
-            std::snprintf(t, sizeof t, " %.4f %.4f", m.t_stage, m.t_conv);
-            return t;
-        }
-    return "";
-}
-
 int fr_debug_plan(fr_handle* h, int B, char* buf, size_t n) {
     if (!h || !buf || n == 0 || B <= 0) { set_error("fr_debug_plan: bad argument"); return FR_ERR_ARG; }
     std::string out;
     const std::vector<char> stage_run = stage_plan(h, B);
     for (const auto& op : h->ops) {
         if (op_skipped(op, stage_run)) continue;
-        if (op.kind == OP_STAGE && h->stages[op.stage].trans) {  // M x 64 x 2944 MACs = conv1 + conv2 + downsample
-            const StageRec& r = h->stages[op.stage];
-            out += "trans " + std::to_string(B * 3136) + " 64 2944 2944 1 1 3x3 " + h->tensors[r.out].name +
-                   meas_note(h, op.grp, B) + "\n";
-            continue;
-        }
-        if (op.kind == OP_STAGE && h->stages[op.stage].stem) {  // M = faces, K = the three convs' MACs per face
-            const StageRec& r = h->stages[op.stage];
-            out += "stem160 " + std::to_string(B) + " 1 185697536 185697536 1 1 3x3 " + h->tensors[r.out].name +
-                   meas_note(h, op.grp, B) + "\n";
-            continue;
-        }
-        if (op.kind == OP_STAGE && h->stages[op.stage].chain == 56) {  // the conv: M x 64 x 392 MACs
-            const StageRec& r = h->stages[op.stage];
-            out += "chain " + std::to_string(B * 3136) + " 64 392 392 1 1 7x7 " + h->tensors[r.out].name +
-                   meas_note(h, op.grp, B) + "\n";
-            continue;
-        }
-        if (op.kind == OP_STAGE && h->stages[op.stage].chain == 28) {  // per block: M x 256 x 272 MACs (69,632 per pixel;
-                                                                        // layer1.0 288)
-            const StageRec& r = h->stages[op.stage];
-            out += "chain " + std::to_string(B * 784) + " 256 272 272 " + std::to_string(r.nblk) + " 1 3x3 " +
-                   h->tensors[r.out].name + meas_note(h, op.grp, B) + "\n";
-            continue;
-        }
-        if (op.kind == OP_STAGE && h->stages[op.stage].chain == 50) {  // per block: M x 1024 x 1088 MACs (1,114,112 per pixel)
-            const StageRec& r = h->stages[op.stage];
-            out += "chain " + std::to_string(B * 49) + " 1024 1088 1088 " + std::to_string(r.nblk) + " 1 3x3 " +
-                   h->tensors[r.out].name + meas_note(h, op.grp, B) + "\n";
-            continue;
-        }
-        if (op.kind == OP_STAGE && h->stages[op.stage].chain == 35) {  // per block: M x 256 x 300 MACs (76,800 per pixel)
-            const StageRec& r = h->stages[op.stage];
-            out += "chain " + std::to_string(B * 289) + " 256 300 300 " + std::to_string(r.nblk) + " 1 3x3 " +
-                   h->tensors[r.out].name + meas_note(h, op.grp, B) + "\n";
-            continue;
-        }
-        if (op.kind == OP_STAGE && h->stages[op.stage].chain) {  // per block: M x 896 x 768 MACs (688,128 per pixel)
-            const StageRec& r = h->stages[op.stage];
-            out += "chain " + std::to_string(B * 64) + " 896 768 768 " + std::to_string(r.nblk) + " 1 1x1 " +
-                   h->tensors[r.out].name + meas_note(h, op.grp, B) + "\n";
-            continue;
-        }
         if (op.kind == OP_STAGE) {
-            const StageRec& r = h->stages[op.stage];
-            const std::string K = std::to_string(9 * r.C);
-            out += std::string(r.fp8 ? "stage8 " : "stage ") + std::to_string(B * r.H * r.H) + " " + std::to_string(r.C) + " " + K + " " + K + " " +
-                   std::to_string(2 * r.nblk) + " 1 3x3 " + h->tensors[r.out].name + meas_note(h, op.grp, B) + "\n";
+            out += stage_plan_line(h, op, B);
             continue;
         }
         if (op.kind != OP_CONV && op.kind != OP_HEAD) {

@@ -458,11 +458,7 @@ hipError_t launch_match_topk(const float* P, int B, const float* G, int64_t N, i
         if (rows_per_split > 64 * MG) return hipErrorInvalidValue;  // the plan's bound (32-bit DMA offsets)
         // lists exactly as deep as needed for the usual k <= 5 (top-5 is the reference's default)
         auto kern = k <= 5 ? match_p512_kernel<5> : match_p512_kernel<8>;
-        static bool attr[2] = {false, false};
-        if (!attr[k <= 5]) {
-            (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, P512_LDS);
-            attr[k <= 5] = true;
-        }
+        if (hipError_t e = lds_opt_in((const void*)kern, P512_LDS); e != hipSuccess) return e;
         hipLaunchKernelGGL(kern, grid, dim3(256), P512_LDS, s, P, B, G, N, k, index_base, rows_per_split, n_split,
                            cand_s, cand_i);
         return hipGetLastError();

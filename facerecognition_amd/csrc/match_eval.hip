@@ -367,20 +367,12 @@ hipError_t launch_match_eval(const float* P, int B, const float* G, int64_t N, i
     const dim3 grid((B + MP - 1) / MP, n_split);
     const size_t hist_b = (size_t)4 * a.nbins * sizeof(uint32_t);
     if (D == D512 && a.rows_per_split <= 64 * MG) {  // (32-bit DMA offsets: at most 64 tiles per split)
-        static bool attr = false;
-        if (!attr) {
-            (void)hipFuncSetAttribute((const void*)eval_p512_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                      P512_LDS + 4 * 2048 * (int)sizeof(uint32_t));
-            attr = true;
-        }
+        const int max_lds = P512_LDS + 4 * 2048 * (int)sizeof(uint32_t);
+        if (hipError_t e = lds_opt_in((const void*)eval_p512_kernel, max_lds); e != hipSuccess) return e;
         hipLaunchKernelGGL(eval_p512_kernel, grid, dim3(256), P512_LDS + hist_b, s, a);
     } else {
-        static bool attr = false;
-        if (!attr) {  // static 51.4 KB + up to 32 KB of histograms
-            (void)hipFuncSetAttribute((const void*)eval_partial_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                      4 * 2048 * (int)sizeof(uint32_t));
-            attr = true;
-        }
+        const int max_lds = 4 * 2048 * (int)sizeof(uint32_t);  // static 51.4 KB + up to 32 KB of histograms
+        if (hipError_t e = lds_opt_in((const void*)eval_partial_kernel, max_lds); e != hipSuccess) return e;
         hipLaunchKernelGGL(eval_partial_kernel, grid, dim3(256), hist_b, s, a);
     }
     return hipGetLastError();

@@ -101,6 +101,38 @@ def test_chain_graph_replay_repeatable(gpu):
         assert np.array_equal(o, outs[0])
 
 
+# ---- FR_OPT_FUSED_MASK: one bit per fused-stage kind (include/frhip.h).  Under FR_OPT_STAGE = 2 a single bit turns on
+# exactly its kind's plan lines in the model that has the kind, and no fused line in the other models.
+_FUSED_LABELS = ("trans ", "stem160 ", "chain ", "stage ", "stage8 ")
+_FUSED_LINES = {  # arch -> bit -> line prefixes at B = 2 ("<label> M N K Kpad units split kernel")
+    "iresnet100": {1: ["trans 6272 64 2944 2944 1 1 3x3 ", "stage 392 256 2304 2304 ", "stage 1568 128 1152 1152 ",
+                       "stage 6272 64 576 576 "]},
+    "irv1_facenet": {2: ["stem160 2 1 185697536 185697536 1 1 3x3 "], 4: ["chain 578 256 300 300 5 1 3x3 "],
+                     8: ["chain 128 896 768 768 10 1 1x1 "]},
+    # (bit 32: the block count depends on whether layer1.0's downsample folds into its conv3)
+    "resnet50_arcface": {16: ["chain 98 1024 1088 1088 5 1 3x3 "], 32: ["chain 1568 256 272 272 "],
+                         64: ["chain 6272 64 392 392 1 1 7x7 "]},
+}
+
+
+@pytest.mark.parametrize("arch", sorted(_FUSED_LINES))
+def test_fused_mask_bit_selects_its_kind(gpu, arch):
+    from facerecognition_amd.model import FRModel
+    m = FRModel.synthetic(arch, dtype="bf16")
+    m.set_option(N.FR_OPT_STAGE, 2)
+    plans = {}
+    for bit in (1, 2, 4, 8, 16, 32, 64):
+        m.set_option(N.FR_OPT_FUSED_MASK, bit)
+        plans[bit] = [ln for ln in _plan(m, 2).splitlines() if ln.startswith(_FUSED_LABELS)]
+    m.close()
+    for bit, fused in plans.items():
+        want = _FUSED_LINES[arch].get(bit, [])
+        print(f"{arch} mask {bit}: {fused}")
+        assert len(fused) == len(want), f"{arch} mask {bit}: fused plan lines {fused}, expected prefixes {want}"
+        for prefix in want:
+            assert sum(ln.startswith(prefix) for ln in fused) == 1, f"{arch} mask {bit}: no single line '{prefix}' in {fused}"
+
+
 # ---- the IRV1 stem as one launch (conv_stem160.hip: conv2d_1a .. conv2d_3b, row rings in LDS; with u8 crops it
 # also prepares the input itself)
 @pytest.mark.parametrize("fmt", ["u8", "f32"])
