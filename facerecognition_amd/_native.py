@@ -66,6 +66,15 @@ class FrConvDesc(ctypes.Structure):
     ]
 
 
+class FrConvExt(ctypes.Structure):
+    _fields_ = [
+        ("x2", c_void_p), ("H2", c_int), ("W2", c_int), ("Cx2", c_int), ("x2_off", c_int), ("C2", c_int), ("st2", c_int),
+        ("y_bf16", c_int),
+        ("splitk_cnt", c_void_p),
+        ("amax_slots", c_int),
+    ]
+
+
 _SIGS = {
     "fr_last_error": (ctypes.c_char_p, []),
     "fr_abi_version": (c_int, []),
@@ -128,6 +137,14 @@ _SIGS = {
     "fr_op_avgpool": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_int, c_void_p]),
     "fr_op_linear": (c_int, [c_void_p, c_int, c_int, c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_void_p,
                              c_int, c_void_p, c_int, c_void_p]),
+    "fr_op_conv2d_ex": (c_int, [ctypes.POINTER(FrConvDesc), ctypes.POINTER(FrConvExt), c_void_p]),
+    "fr_op_head_gemv": (c_int, [c_void_p, c_int, c_int, c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_void_p,
+                                c_int, c_void_p, c_int, c_void_p]),
+    "fr_op_proj_l2": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p]),
+    "fr_op_l2norm_rows": (c_int, [c_void_p, c_int, c_int, c_void_p]),
+    "fr_op_amax": (c_int, [c_void_p, c_size_t, c_int, c_void_p, c_int, c_void_p]),
+    "fr_op_maxpool_cvt": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p,
+                                  c_int, c_int, c_int, c_int, c_void_p]),
 }
 
 _lib = None

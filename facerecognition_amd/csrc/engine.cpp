@@ -2544,7 +2544,16 @@ int fr_debug_copy_tensor(fr_handle* h, int t, int B, void* dst, void* stream) {
     return FR_OK;
 }
 
-int fr_op_conv2d(const fr_conv_desc* d, void* stream) {
+int fr_op_conv2d(const fr_conv_desc* d, void* stream) { return fr_op_conv2d_ex(d, nullptr, stream); }
+
+// The tile ids fr_op_conv2d_ex hands to launch_conv (0 = the cost model's choice, an implicit-GEMM tile too)
+static bool op_tile_is_igemm(int tile) {
+    if (tile == 0) return true;
+    const int t = tile - 1;
+    return (t >= 0 && t < NUM_TILE_IDS && t != FR_TILE_BAND) || t == TILE_64x64_S3 || t == TILE_64x64 || t == TILE_32x64_S3;
+}
+
+int fr_op_conv2d_ex(const fr_conv_desc* d, const fr_conv_ext* e, void* stream) {
     if (!d || !d->x || !d->w || !d->y || d->B <= 0 || d->Cin <= 0 || d->Cin % 8 || d->Cx % 8 || d->x_off % 8 ||
         d->Cout <= 0 || d->Cout % 8 || d->Cy % 8 || d->y_off % 8 || d->Npad % 128 || d->Kpad % 64 ||
         d->Npad < d->Cout || d->Kpad < d->Kh * d->Kw * d->Cin || d->x_off + d->Cin > d->Cx ||
@@ -2567,6 +2576,46 @@ int fr_op_conv2d(const fr_conv_desc* d, void* stream) {
     a.f16 = d->dtype == FR_DTYPE_F16;
     a.y_amax = d->y_amax;
     a.amax_slots = 1;
+    int* splitk_cnt = nullptr;
+    if (e) {
+        // every refusal is made here, on the host, before any launch: a kernel that cannot run a field never sees it
+        const auto refuse = [](const char* why) {
+            set_error(std::string("fr_op_conv2d_ex: ") + why);
+            return FR_ERR_ARG;
+        };
+        const int tile = d->tile;
+        const bool igemm = op_tile_is_igemm(tile);
+        const bool wring = tile == FR_TILE_WRING + 1, small = tile == FR_TILE_SMALL + 1, direct = tile == FR_TILE_DIRECT + 1;
+        if (e->amax_slots < 0) return refuse("amax_slots < 0");
+        if (e->amax_slots > 0) a.amax_slots = e->amax_slots;
+        if (e->x2) {
+            if (d->dtype == FR_DTYPE_FP8) return refuse("the K-concatenated projection (x2) has no fp8 kernel");
+            if (!igemm && !wring && !small)
+                return refuse("the K-concatenated projection (x2) runs on the implicit-GEMM tiles, FR_TILE_WRING and "
+                              "FR_TILE_SMALL only (not band / rows / img / direct)");
+            if (e->st2 <= 0 || e->H2 <= 0 || e->W2 <= 0 || e->C2 <= 0 || e->x2_off < 0 || e->Cx2 % 8 || e->x2_off % 8 ||
+                d->Cin % 64 || e->C2 % 64 || a.K + e->C2 > d->Kpad || e->x2_off + e->C2 > e->Cx2 ||
+                (a.Ho - 1) * e->st2 >= e->H2 || (a.Wo - 1) * e->st2 >= e->W2)
+                return refuse("bad projection (x2): needs Cin % 64 == 0, C2 % 64 == 0, Kh*Kw*Cin + C2 <= Kpad, "
+                              "x2_off + C2 <= Cx2, Cx2 % 8 == 0, x2_off % 8 == 0, (Ho-1)*st2 < H2, (Wo-1)*st2 < W2");
+            a.x2 = (const bf16_t*)e->x2; a.H2 = e->H2; a.W2 = e->W2; a.Cx2 = e->Cx2; a.x2_off = e->x2_off;
+            a.C2 = e->C2; a.st2 = e->st2; a.K1 = a.K;
+            a.K = a.K1 + a.C2;
+        }
+        if (e->y_bf16) {
+            if (d->dtype != FR_DTYPE_F16 || d->res || d->y2) return refuse("y_bf16 needs FR_DTYPE_F16 and neither res nor y2");
+            if (!igemm && !wring && !small && !direct)
+                return refuse("y_bf16 runs on the implicit-GEMM tiles, FR_TILE_WRING, FR_TILE_SMALL and FR_TILE_DIRECT only");
+            a.y_bf16 = 1;
+        }
+        if (e->splitk_cnt) {
+            if (!igemm || d->dtype == FR_DTYPE_FP8) return refuse("splitk_cnt (in-launch split-K) is for the implicit-GEMM tiles only");
+            // (the in-launch slabs are addressed by 32-bit buffer offsets)
+            if (d->split_k > 1 && (size_t)d->split_k * a.M * a.Npad * sizeof(float) >= 0x7fffffffull)
+                return refuse("splitk_cnt: the partial workspace must stay below 2 GiB");
+            splitk_cnt = e->splitk_cnt;
+        }
+    }
     if (d->dtype == FR_DTYPE_FP8) {
         if (!d->wscale || !d->x_amax || d->Cin % 64 || d->Kpad % 128 || d->split_k > 1) {
             set_error("fr_op_conv2d: fp8 needs wscale, x_amax, Cin % 64 == 0, Kpad % 128 == 0, no split-K");
@@ -2693,8 +2742,9 @@ int fr_op_conv2d(const fr_conv_desc* d, void* stream) {
         if (!d->partial) { set_error("fr_op_conv2d: split_k > 1 needs partial workspace"); return FR_ERR_ARG; }
         a.split_k = d->split_k;
         a.partial = d->partial;
+        a.splitk_cnt = splitk_cnt;  // non-null: the tiles' last workgroups reduce, no second launch
         FR_HIP_CHECK(launch_conv(a, (hipStream_t)stream));
-        FR_HIP_CHECK(launch_splitk_epilogue(a, (hipStream_t)stream));
+        if (!a.splitk_cnt) FR_HIP_CHECK(launch_splitk_epilogue(a, (hipStream_t)stream));
     } else {
         a.split_k = 1;
         FR_HIP_CHECK(launch_conv(a, (hipStream_t)stream));
@@ -2779,6 +2829,57 @@ int fr_op_linear(const void* x, int B, int K, const void* w, int N, int Npad, in
     }
     FR_HIP_CHECK(launch_conv(a, (hipStream_t)stream));
     FR_HIP_CHECK(launch_head_finalize(partial, split_k, B, N, Npad, bias, normalize, out, (hipStream_t)stream));
+    return FR_OK;
+}
+
+int fr_op_head_gemv(const void* x, int B, int K, const void* w, int N, int Npad, int Kpad, const float* bias,
+                    int normalize, float* out, int S, float* partial, int dtype, void* stream) {
+    if (!x || !w || !out || !partial || K <= 0 || N <= 0 || Npad < N || S < 1 || Kpad % 8 || N % 4 || N > 1024 ||
+        (dtype != FR_DTYPE_BF16 && dtype != FR_DTYPE_F16) || !head_gemv_supported(B, K, Kpad, Npad)) {
+        set_error("fr_op_head_gemv: bad argument (1 <= B <= 8, K % 8 == 0, Kpad % 8 == 0, Kpad >= K, Npad % 16 == 0, "
+                  "N % 4 == 0, N <= 1024, S >= 1, bf16 / f16)");
+        return FR_ERR_ARG;
+    }
+    FR_HIP_CHECK(launch_head_gemv((const bf16_t*)x, B, K, (const bf16_t*)w, Kpad, N, Npad, S, dtype == FR_DTYPE_F16,
+                                  partial, (hipStream_t)stream));
+    FR_HIP_CHECK(launch_head_finalize(partial, S, B, N, Npad, bias, normalize, out, (hipStream_t)stream));
+    return FR_OK;
+}
+
+int fr_op_proj_l2(const float* x, int B, int K, const float* W, const float* bias, int N, int normalize, float* out,
+                  void* stream) {
+    if (!x || !W || !out || B <= 0 || K <= 0 || K > 1024 || N <= 0) {
+        set_error("fr_op_proj_l2: bad argument (1 <= K <= 1024)");
+        return FR_ERR_ARG;
+    }
+    FR_HIP_CHECK(launch_proj_l2(x, B, K, W, bias, N, normalize, out, (hipStream_t)stream));
+    return FR_OK;
+}
+
+int fr_op_l2norm_rows(float* x, int B, int D, void* stream) {
+    if (!x || B <= 0 || D <= 0) { set_error("fr_op_l2norm_rows: bad argument"); return FR_ERR_ARG; }
+    FR_HIP_CHECK(launch_l2norm_rows(x, B, D, (hipStream_t)stream));
+    return FR_OK;
+}
+
+int fr_op_amax(const void* x, size_t n, int dtype, float* amax, int slots, void* stream) {
+    if (!x || !amax || n == 0 || n % 8 || slots < 1 || (dtype != FR_DTYPE_BF16 && dtype != FR_DTYPE_F16)) {
+        set_error("fr_op_amax: bad argument (n % 8 == 0, slots >= 1, bf16 / f16)");
+        return FR_ERR_ARG;
+    }
+    FR_HIP_CHECK(launch_amax((const bf16_t*)x, n, dtype == FR_DTYPE_F16, amax, slots, (hipStream_t)stream));
+    return FR_OK;
+}
+
+int fr_op_maxpool_cvt(const void* x, int B, int H, int W, int Cx, int x_off, int C, int k, int stride, int pad, void* y,
+                      int Cy, int y_off, int Ho, int Wo, void* stream) {
+    if (!x || !y || B <= 0 || C <= 0 || C % 8 || Cx % 8 || x_off % 8 || Cy % 8 || y_off % 8 || k != 3 || stride <= 0 ||
+        pad < 0 || pad >= k) {
+        set_error("fr_op_maxpool_cvt: bad argument (the f16 -> bf16 pool is 3x3 only)");
+        return FR_ERR_ARG;
+    }
+    FR_HIP_CHECK(launch_maxpool((const bf16_t*)x, B, H, W, Cx, x_off, C, k, stride, pad, (bf16_t*)y, Cy, y_off, Ho, Wo, 1,
+                                (hipStream_t)stream, 1));
     return FR_OK;
 }
 

@@ -291,6 +291,29 @@ typedef struct fr_conv_desc {
 
 int fr_op_conv2d(const fr_conv_desc* d, void* stream);
 
+/* The conv paths a forward plan reaches but fr_conv_desc cannot express (kernel parity tests).  A NULL or
+ * all-zero ext is fr_op_conv2d.  Every combination a kernel cannot run is refused with FR_ERR_ARG (a message
+ * naming fr_op_conv2d_ex), never run by another kernel. */
+typedef struct fr_conv_ext {
+    /* K-concatenated 1x1 projection (a residual block's downsample folded into its last conv): K steps
+     * [K1, K1 + C2), K1 = Kh*Kw*Cin, read x2 [B,H2,W2,Cx2] at (oh * st2, ow * st2), channels
+     * [x2_off, x2_off + C2); the weight rows are [W_conv | W_proj | 0-pad] and bias is the sum of both.
+     * Needs Cin % 64 == 0, C2 % 64 == 0, K1 + C2 <= Kpad, (Ho-1)*st2 < H2, (Wo-1)*st2 < W2,
+     * x2_off + C2 <= Cx2, Cx2 % 8 == 0, x2_off % 8 == 0.  The implicit-GEMM tiles, FR_TILE_WRING and
+     * FR_TILE_SMALL take it (the latter two where their own shape rules hold); not FR_DTYPE_FP8. */
+    const void* x2; int H2, W2, Cx2, x2_off, C2, st2;
+    /* dtype FR_DTYPE_F16 with y stored as bf16 (the end of an f16 section of a bf16 plan): no res, no y2;
+     * the implicit-GEMM tiles, FR_TILE_WRING, FR_TILE_SMALL and FR_TILE_DIRECT. */
+    int y_bf16;
+    /* split_k > 1 on an implicit-GEMM tile: per-tile arrival counters (one int per pixels x channels tile,
+     * zero before the call and zero again after it).  Non-NULL: a single launch, the last workgroup of each
+     * tile sums the partials in split order and runs the epilogue (the bits of the two-launch reduction). */
+    int* splitk_cnt;
+    /* y_amax is an array of this many partial maxima (0 = 1); max |y| is the maximum over them. */
+    int amax_slots;
+} fr_conv_ext;
+int fr_op_conv2d_ex(const fr_conv_desc* d, const fr_conv_ext* e, void* stream);
+
 /* u8 NHWC [B,H,W,3] or f32 NCHW [B,3,H,W] → 16-bit NHWC [B,H,W,8] = [q0,q1,q2,q0,q1,q2,0,0] with
  * q = 2u-255 (u8; exact) or q = 255*x (normalized f32), i.e. q = 255 * ((u/255-0.5)/0.5).  The stem
  * conv weights carry 1/255 as a hi/lo pair on the duplicated channels (exact first layer). */
@@ -307,6 +330,30 @@ int fr_op_avgpool(const void* x, int B, int H, int W, int C, void* y, int dtype,
  * normalize (F.normalize eps 1e-12).  `partial` must hold split_k*B*Npad floats. */
 int fr_op_linear(const void* x, int B, int K, const void* w, int N, int Npad, int Kpad,
                  const float* bias, int normalize, float* out, int split_k, float* partial, int dtype, void* stream);
+
+/* The small-batch head of the online path (B <= 8 probes): the same result as fr_op_linear from the GEMV
+ * kernel, S chunks of K as split-K partials (`partial` holds S*B*Npad floats), then the head's finalize
+ * (bias, optional L2 normalize).  K % 8 == 0, Kpad % 8 == 0, Npad % 16 == 0, N % 4 == 0, N <= 1024;
+ * w has Npad rows of Kpad elements.  Anything else is refused (FR_ERR_ARG). */
+int fr_op_head_gemv(const void* x, int B, int K, const void* w, int N, int Npad, int Kpad, const float* bias,
+                    int normalize, float* out, int S, float* partial, int dtype, void* stream);
+
+/* FaceNet projection: out [B,N] = x [B,K] . W [N,K]^T + bias (all f32; bias may be NULL), optional
+ * F.normalize (eps 1e-12).  1 <= K <= 1024. */
+int fr_op_proj_l2(const float* x, int B, int K, const float* W, const float* bias, int N, int normalize,
+                  float* out, void* stream);
+
+/* Row-wise L2 normalize of x [B,D] f32 in place (F.normalize, eps 1e-12). */
+int fr_op_l2norm_rows(float* x, int B, int D, void* stream);
+
+/* max |x| of n 16-bit values (n % 8 == 0) raised into amax[0 .. slots): the maximum over the slots, combined
+ * with what they held before, is max |x| (the caller zeroes them for a fresh maximum). */
+int fr_op_amax(const void* x, size_t n, int dtype, float* amax, int slots, void* stream);
+
+/* fr_op_maxpool from an f16 tensor into a bf16 one (the end of an f16 section of a bf16 plan): each
+ * maximum rounded to bf16 once, to nearest even.  k == 3 only. */
+int fr_op_maxpool_cvt(const void* x, int B, int H, int W, int Cx, int x_off, int C, int k, int stride, int pad,
+                      void* y, int Cy, int y_off, int Ho, int Wo, void* stream);
 
 /* ---- execution options (no reference counterpart: plan choices of this build) ----------------
  * FR_OPT_STAGE (default 1; FR_AB no_stage starts at 0): run the stride-1 IResNet100 layer3 blocks

