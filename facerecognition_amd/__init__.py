@@ -20,8 +20,13 @@ def __getattr__(name):  # lazy: importing the package must not initialise the GP
     if name in _EVALUATE:
         from . import evaluate
         return getattr(evaluate, name)
+    if name in _EXPLAIN:
+        from . import explainability
+        return getattr(explainability, name)
     raise AttributeError(name)
 
 
+_EXPLAIN = ("ExplainabilityEngine", "FaceNetExplainabilityEngine", "generate_heatmap", "overlay_heatmap",
+            "explain_prediction", "cam_closed_form")
 _EVALUATE = ("compute_metrics", "threshold_sweep", "roc_analysis", "generate_report", "evaluate_recognition_engine",
              "closed_set_report", "evaluate_closed_set")

@@ -85,6 +85,12 @@ _SIGS = {
     "fr_embed_dim": (c_int, [c_void_p]),
     "fr_input_size": (c_int, [c_void_p]),
     "fr_embed": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_int, c_void_p]),
+    "fr_explain_shape": (c_int, [c_void_p, ctypes.POINTER(c_int), ctypes.POINTER(c_int), ctypes.POINTER(c_int)]),
+    "fr_explain": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
+                           c_void_p]),
+    "fr_op_head_grad": (c_int, [c_void_p, c_int, c_int, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p]),
+    "fr_op_cam": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_int, c_int, c_void_p, c_void_p,
+                          c_void_p]),
     "fr_gallery_set": (c_int, [c_void_p, c_void_p, c_int64, c_int, c_int64, c_int]),
     "fr_gallery_rows": (c_int64, [c_void_p]),
     "fr_gallery_write": (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_int, c_int]),

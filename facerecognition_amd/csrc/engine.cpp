@@ -117,6 +117,7 @@ void free_acts(fr_handle* h) {
     h->splitk_cnt = nullptr;
     h->emb_pre = nullptr;
     h->amax = nullptr;
+    h->ex_g = h->ex_v = h->ex_emb = nullptr;
     h->max_batch = 0;
 }
 
@@ -603,6 +604,8 @@ void build_iresnet100(Builder& b) {
         close_stage(true);
         H = Ho;
     }
+    h->ex_tensor = x;  // fr_explain: Grad-CAM on layer4.2, which the head reads flattened (NHWC order)
+    h->ex_layout = 1;
     b.head(x);
 }
 
@@ -767,6 +770,8 @@ void build_resnet50(Builder& b) {
             b.close_stage(ch_op, ch);
         }
     }
+    h->ex_tensor = x;  // fr_explain: Grad-CAM on backbone.layer4 (the avg-pool's input)
+    h->ex_layout = 0;
     const int pool = b.tensor(1, 1, C, "backbone.avgpool");
     b.avgpool(x, pool);
     b.head(pool);
@@ -933,6 +938,13 @@ void build_irv1(Builder& b) {
         b.conv({p + "conv2d"}, cat, 192, 384, y, 0, 1, 1, 1, 1, 0, 0, i < 5 ? 1 : 0, x, 0);
         x = y;
     }
+    // fr_explain: the activation map of block8.conv2d's own output.  That conv writes conv + x, so fr_explain runs
+    // it once more without the residual into this scratch tensor (never the difference of two bf16 tensors)
+    if (!b.rc) {
+        h->ex_conv = (int)h->ops.size() - 1;
+        h->ex_tensor = b.tensor(3, 3, 1792);
+        h->ex_layout = 2;
+    }
     const int pool = b.tensor(1, 1, 1792, m + "avgpool_1a");
     b.avgpool(x, pool);
     b.head(pool);
@@ -997,6 +1009,21 @@ int reserve(fr_handle* h, int maxB) {
         if (rc) { free_acts(h); return rc; }
         h->act_allocs.push_back(q);
         h->emb_pre = (float*)q;
+    }
+    if (h->ex_tensor >= 0) {  // fr_explain's scratch (the gradient buffers only where a gradient is taken)
+        const DevConvW& hw = h->convw[h->ops.back().wi];  // the head is every plan's last op
+        const size_t D = (size_t)(h->proj_d ? h->proj_d : h->embed_dim);
+        float** dst[3] = {&h->ex_emb, &h->ex_g, &h->ex_v};
+        const size_t n[3] = {maxB * D, h->ex_layout == 2 ? 0 : maxB * (size_t)hw.Cout,
+                             h->ex_layout == 2 ? 0 : maxB * (size_t)hw.Kpad};
+        for (int i = 0; i < 3; ++i) {
+            if (!n[i]) continue;
+            void* q = nullptr;
+            rc = dev_alloc(&q, n[i] * sizeof(float));
+            if (rc) { free_acts(h); return rc; }
+            h->act_allocs.push_back(q);
+            *dst[i] = (float*)q;
+        }
     }
     if (std::any_of(h->stages.begin(), h->stages.end(), [](const StageRec& r) { return r.parts > 1; })) {
         if (h->stages.size() > FR_MAX_SPLIT_STAGES) { set_error("reserve: too many stage ops"); return FR_ERR_ARG; }
@@ -1789,6 +1816,7 @@ int fr_load_weights(fr_handle* h, const void* blob, size_t nbytes) {
     h->tensors.clear();
     h->ops.clear();
     h->loaded = false;
+    h->ex_tensor = h->ex_conv = -1;
     Builder b{h, W};
     if (h->arch == FR_ARCH_IRESNET100) build_iresnet100(b);
     else if (h->arch == FR_ARCH_RESNET50_ARCFACE) build_resnet50(b);
@@ -1983,6 +2011,64 @@ int fr_embed(fr_handle* h, const void* in, int in_fmt, int B, int H, int W, floa
     if (!h) { set_error("fr_embed: null handle"); return FR_ERR_ARG; }
     std::lock_guard<std::mutex> lk(h->mu);
     return embed_locked(h, in, in_fmt, B, H, W, out, flags, stream);
+}
+
+int fr_explain_shape(const fr_handle* h, int* th, int* tw, int* tc) {
+    if (!h || !th || !tw || !tc) { set_error("fr_explain_shape: null argument"); return FR_ERR_ARG; }
+    if (!h->loaded || h->ex_tensor < 0) { set_error("fr_explain_shape: weights not loaded"); return FR_ERR_STATE; }
+    const auto& t = h->tensors[h->ex_tensor];
+    *th = t.H; *tw = t.W; *tc = t.C;
+    return FR_OK;
+}
+
+int fr_explain(fr_handle* h, const void* in, int in_fmt, int B, int H, int W, const float* target, float* cam,
+               float* low, float* emb, void* stream) {
+    if (!h) { set_error("fr_explain: null handle"); return FR_ERR_ARG; }
+    std::lock_guard<std::mutex> lk(h->mu);
+    if (!h->loaded || h->ex_tensor < 0) { set_error("fr_explain: weights not loaded"); return FR_ERR_STATE; }
+    if (!cam) { set_error("fr_explain: cam is NULL"); return FR_ERR_ARG; }
+    if (!in || B <= 0) { set_error("fr_explain: bad argument"); return FR_ERR_ARG; }
+    if (h->max_batch <= 0) { set_error("fr_explain: nothing reserved (call fr_reserve first)"); return FR_ERR_STATE; }
+    if (B > h->max_batch) {
+        set_error("fr_explain: B = " + std::to_string(B) + " is above the reserved batch " + std::to_string(h->max_batch) +
+                  " (fr_reserve)");
+        return FR_ERR_ARG;
+    }
+    if (B > embed_chunk(h)) {  // a chunked forward leaves only its last chunk's activations behind
+        set_error("fr_explain: B is above the largest single forward (" + std::to_string(embed_chunk(h)) + ")");
+        return FR_ERR_ARG;
+    }
+    float* e = emb ? emb : h->ex_emb;
+    // the forward: waited for and re-run when a split stage's wait ran out (no FR_EMBED_ASYNC), so the explained
+    // tensor below is that of valid embeddings; B <= max_batch, so nothing is re-reserved
+    int rc = embed_locked(h, in, in_fmt, B, H, W, e, FR_EMBED_RAW, stream);
+    if (rc) return rc;
+    const hipStream_t s = (hipStream_t)stream;
+    const int f16 = h->dtype == FR_DTYPE_F16;
+    const auto& t = h->tensors[h->ex_tensor];
+    if (!cam_supported(B, t.H, t.W, t.C, h->in_size)) {
+        set_error("fr_explain: explained tensor out of the map kernel's range");
+        return FR_ERR_ARG;
+    }
+    if (h->ex_layout == 2) {
+        Op op = h->ops[h->ex_conv];  // block8.conv2d without its residual
+        op.res = -1;
+        op.out = h->ex_tensor;
+        op.out_off = 0;
+        if ((rc = run_conv_op(h, op, B, f16, s))) return rc;
+        FR_HIP_CHECK(launch_cam(t.dev, B, t.H, t.W, t.C, f16 || t.f16, nullptr, 0, 2, h->in_size, cam, low, s));
+        return FR_OK;
+    }
+    const DevConvW& hw = h->convw[h->ops.back().wi];
+    const int need = h->ex_layout == 0 ? t.C : t.H * t.W * t.C;
+    if (hw.K != need || !head_grad_supported(B, hw.Cout, hw.K, hw.Kpad)) {
+        set_error("fr_explain: head shape does not match the explained tensor");
+        return FR_ERR_ARG;
+    }
+    FR_HIP_CHECK(launch_score_grad(e, target, B, hw.Cout, h->ex_g, s));
+    FR_HIP_CHECK(launch_head_grad(h->ex_g, B, hw.Cout, hw.w, hw.K, hw.Kpad, f16, h->ex_v, s));
+    FR_HIP_CHECK(launch_cam(t.dev, B, t.H, t.W, t.C, f16 || t.f16, h->ex_v, hw.Kpad, h->ex_layout, h->in_size, cam, low, s));
+    return FR_OK;
 }
 
 int fr_gallery_set(fr_handle* h, const float* G, int64_t N, int D, int64_t index_base, int g_on_device) {
@@ -2843,6 +2929,28 @@ int fr_op_head_gemv(const void* x, int B, int K, const void* w, int N, int Npad,
     FR_HIP_CHECK(launch_head_gemv((const bf16_t*)x, B, K, (const bf16_t*)w, Kpad, N, Npad, S, dtype == FR_DTYPE_F16,
                                   partial, (hipStream_t)stream));
     FR_HIP_CHECK(launch_head_finalize(partial, S, B, N, Npad, bias, normalize, out, (hipStream_t)stream));
+    return FR_OK;
+}
+
+int fr_op_head_grad(const float* g, int B, int N, const void* w, int K, int Kpad, int dtype, float* v, void* stream) {
+    if (!g || !w || !v || (dtype != FR_DTYPE_BF16 && dtype != FR_DTYPE_F16) || !head_grad_supported(B, N, K, Kpad)) {
+        set_error("fr_op_head_grad: bad argument (B >= 1, 1 <= N <= 1024, K % 8 == 0, Kpad % 8 == 0, Kpad >= K, bf16 / f16)");
+        return FR_ERR_ARG;
+    }
+    FR_HIP_CHECK(launch_head_grad(g, B, N, (const bf16_t*)w, K, Kpad, dtype == FR_DTYPE_F16, v, (hipStream_t)stream));
+    return FR_OK;
+}
+
+int fr_op_cam(const void* act, int B, int h, int w, int C, int dtype, const float* v, int v_layout, int S, float* cam,
+              float* low, void* stream) {
+    if (!act || !cam || (dtype != FR_DTYPE_BF16 && dtype != FR_DTYPE_F16) || v_layout < 0 || v_layout > 2 ||
+        (v_layout != 2 && !v) || !cam_supported(B, h, w, C, S)) {
+        set_error("fr_op_cam: bad argument (h * w <= 256, C % 8 == 0, C <= 4096, 1 <= S <= 4096, v_layout 0 / 1 with v, "
+                  "2 without, bf16 / f16)");
+        return FR_ERR_ARG;
+    }
+    FR_HIP_CHECK(launch_cam((const bf16_t*)act, B, h, w, C, dtype == FR_DTYPE_F16, v, v_layout == 0 ? C : h * w * C,
+                            v_layout, S, cam, low, (hipStream_t)stream));
     return FR_OK;
 }
 

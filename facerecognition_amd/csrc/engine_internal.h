@@ -209,6 +209,14 @@ struct fr_handle {
     bool invariant = false;
     int fused_mask = 127;  // FR_OPT_FUSED_MASK
     const uint8_t* fwd_u8 = nullptr;  // the current forward's u8 crops when a fused stem prepares them itself
+    // fr_explain (explain.hip): the explained tensor, how the head reads it (0 pooled, 1 flattened, 2 = the
+    // activation map of ex_tensor, which op ex_conv writes when run again without its residual), and the scratch
+    // of reserve(): the score gradient [max_batch][embed_dim], the head-input gradient [max_batch][head Kpad] and
+    // the raw embeddings when the caller takes none
+    int ex_tensor = -1, ex_layout = 0, ex_conv = -1;
+    float* ex_g = nullptr;
+    float* ex_v = nullptr;
+    float* ex_emb = nullptr;
 };
 
 #pragma GCC visibility push(hidden)

@@ -295,6 +295,21 @@ hipError_t launch_proj_l2(const float* x, int B, int K, const float* W, const fl
 // Row-wise L2 normalize in place (F.normalize, eps 1e-12).
 hipError_t launch_l2norm_rows(float* x, int B, int D, hipStream_t s);
 
+// Class-activation maps (explain.hip).  g [B][N] = d score / d embedding from the raw embeddings emb [B][N]: 2 emb
+// (target null), else the gradient of F.cosine_similarity(emb, target).
+hipError_t launch_score_grad(const float* emb, const float* target, int B, int N, float* g, hipStream_t s);
+// v [B][Kpad] = g [B][N] . w [N][Kpad] (16-bit weight rows, f32 accumulation in an order that depends on N alone);
+// columns [K, Kpad) are not written.  N <= 1024, K % 8 == 0, Kpad % 8 == 0.
+bool head_grad_supported(int B, int N, int K, int Kpad);
+hipError_t launch_head_grad(const float* g, int B, int N, const bf16_t* w, int K, int Kpad, int f16, float* v,
+                            hipStream_t s);
+// cam [B][S][S] (and low [B][h][w], the map before ReLU, when non-null) of act [B][h][w][C]; layout 0: v [B][v_stride]
+// is the gradient of the pooled input, 1: of the flattened NHWC input, 2: the activation map (v unused).
+// h * w <= 256, C % 8 == 0, C <= 4096.
+bool cam_supported(int B, int h, int w, int C, int S);
+hipError_t launch_cam(const bf16_t* act, int B, int h, int w, int C, int f16, const float* v, int v_stride, int layout,
+                      int S, float* cam, float* low, hipStream_t s);
+
 // Gallery match.
 hipError_t launch_match_topk(const float* P, int B, const float* G, int64_t N, int D, int k,
                              int64_t index_base, float* cand_s, int32_t* cand_i, int n_split,

@@ -116,6 +116,45 @@ class FRModel:
                 "fr_embed")
         return out
 
+    def explain_shape(self):
+        """(h, w, C) of the explained layer (fr_explain_shape)."""
+        h, w, c = ctypes.c_int(), ctypes.c_int(), ctypes.c_int()
+        N.check(N.lib().fr_explain_shape(self._h, ctypes.byref(h), ctypes.byref(w), ctypes.byref(c)),
+                "fr_explain_shape")
+        return h.value, w.value, c.value
+
+    def explain(self, x, target=None, return_low: bool = False):
+        """Class-activation maps of a batch (fr_explain): one forward, then the map kernels on the same stream.
+
+        Replaces GradCAM.generate (inference/explainability.py:76-131) per image: Grad-CAM on the last
+        tensor before the head for the ArcFace backbones, the |block8.conv2d| activation map for IRV1
+        (which ignores ``target``, as the reference's FaceNet engine does).  target: None (score = the
+        squared norm of the raw embedding) or [B, D] / [D] embeddings (score = cosine similarity to them).
+        Returns (cam [B,S,S] f32 in [0, 1], raw embeddings [B,D]) and, with return_low, the map before ReLU
+        [B,h,w] as a third element."""
+        import torch
+
+        x, fmt, H, W = self._prep(x)
+        B = int(x.shape[0])
+        self.reserve(B)  # fr_explain takes no batch above the reserved one (a no-op once reserved)
+        S, D = self.input_size, self.embedding_size
+        t = None
+        if target is not None:
+            if isinstance(target, np.ndarray):
+                target = torch.from_numpy(target)
+            t = target.to(self.device, torch.float32).reshape(-1, D)
+            if t.shape[0] == 1 and B > 1:
+                t = t.expand(B, D)
+            if t.shape[0] != B:
+                raise ValueError(f"target must be [D] or [B, D] with B = {B}, got {tuple(target.shape)}")
+            t = t.contiguous()
+        cam = torch.empty((B, S, S), dtype=torch.float32, device=self.device)
+        emb = torch.empty((B, D), dtype=torch.float32, device=self.device)
+        low = torch.empty((B,) + self.explain_shape()[:2], dtype=torch.float32, device=self.device) if return_low else None
+        N.check(N.lib().fr_explain(self._h, N.ptr(x), fmt, B, H, W, N.ptr(t), N.ptr(cam), N.ptr(low), N.ptr(emb),
+                                   N.stream_ptr(self.device)), "fr_explain")
+        return (cam, emb, low) if return_low else (cam, emb)
+
     def sync_check(self) -> None:
         """Synchronize the current stream; raise if an async forward's split-stage wait ran out."""
         N.check(N.lib().fr_sync_check(self._h, N.stream_ptr(self.device)), "fr_sync_check")

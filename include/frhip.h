@@ -96,6 +96,31 @@ int fr_input_size(const fr_handle* h);
 int fr_embed(fr_handle* h, const void* in, int in_fmt, int B, int H, int W,
              float* out, int flags, void* stream);
 
+/* ---- explanations (replaces GradCAM.generate, inference/explainability.py:76-131, as called by
+ *      ExplainabilityEngine.explain :298-359, and the activation map of FaceNetExplainabilityEngine.explain
+ *      :482-501) ----
+ * No backward pass: everything after the explained tensor is affine in eval mode and folded into the head
+ * matrix, so d score / d tensor = head.w^T . g with g = d score / d embedding in closed form.
+ *   FR_ARCH_RESNET50_ARCFACE  Grad-CAM on backbone.layer4 (= "backbone.layer4.2", the avg-pool's input), as the
+ *                             reference's GradCAM default target.
+ *   FR_ARCH_IRESNET100        Grad-CAM on "layer4.2", the input of bn2 -> flatten -> fc -> features (the reference
+ *                             has no IResNet100 code: this target is this library's choice).
+ *   FR_ARCH_IRV1_FACENET      the activation map |block8.conv2d output| summed over channels (that conv is run
+ *                             once more without its residual, into scratch of fr_reserve); `target` is ignored.
+ * Score: (emb ** 2).sum() when target is NULL, else F.cosine_similarity(emb, target) (norms clamped at 1e-8).
+ * Map: channel weights = mean gradient over positions; low = weighted channel sum per position; ReLU; bilinear
+ * upsample (align_corners = False) to S x S; (c - min) / (max - min) when max > min, else unchanged (IRV1: no
+ * ReLU, zeros when max == min). */
+
+/* Shape of the explained layer (h, w, C) and the map side S (= fr_input_size). */
+int fr_explain_shape(const fr_handle* h, int* th, int* tw, int* tc);
+/* Forward (as fr_embed with FR_EMBED_RAW) + class-activation map, on `stream` in that order.
+ * target [B, D] device f32 or NULL; cam [B,S,S] f32; low [B,th,tw] f32 or NULL (pre-ReLU map);
+ * emb [B,D] f32 or NULL (raw embeddings of this forward).  B must not exceed the batch of fr_reserve
+ * (FR_ERR_ARG); weights not loaded or nothing reserved: FR_ERR_STATE. */
+int fr_explain(fr_handle* h, const void* in, int in_fmt, int B, int H, int W, const float* target,
+               float* cam, float* low, float* emb, void* stream);
+
 /* Synchronize `stream`, then report (once) a split-stage wait that ran out in an FR_EMBED_ASYNC forward
  * of this handle since the last report: FR_ERR_STAGE, else FR_OK. */
 int fr_sync_check(fr_handle* h, void* stream);
@@ -354,6 +379,17 @@ int fr_op_amax(const void* x, size_t n, int dtype, float* amax, int slots, void*
  * maximum rounded to bf16 once, to nearest even.  k == 3 only. */
 int fr_op_maxpool_cvt(const void* x, int B, int H, int W, int Cx, int x_off, int C, int k, int stride, int pad,
                       void* y, int Cy, int y_off, int Ho, int Wo, void* stream);
+
+/* fr_explain's head-gradient pass: v [B, Kpad] = g [B, N] (f32) . w [N rows of Kpad 16-bit elements], f32
+ * accumulation; the order of the sum over n depends on N alone (not on B).  Columns [K, Kpad) of v are left
+ * untouched.  N <= 1024, K % 8 == 0, Kpad % 8 == 0, Kpad >= K. */
+int fr_op_head_grad(const float* g, int B, int N, const void* w, int K, int Kpad, int dtype, float* v, void* stream);
+/* fr_explain's map kernel on act [B,h,w,C] (16-bit NHWC): v_layout 0 = v [B, C] is the gradient of the pooled
+ * head input (every position's gradient is v / (h w)); 1 = v [B, h*w*C] is the gradient of the flattened NHWC
+ * tensor; 2 = the activation map sum_c |act| (v NULL).  cam [B,S,S] f32; low [B,h,w] f32 or NULL (the map before
+ * ReLU).  h*w <= 256, C % 8 == 0, C <= 4096. */
+int fr_op_cam(const void* act, int B, int h, int w, int C, int dtype, const float* v, int v_layout, int S, float* cam,
+              float* low, void* stream);
 
 /* ---- execution options (no reference counterpart: plan choices of this build) ----------------
  * FR_OPT_STAGE (default 1; FR_AB no_stage starts at 0): run the stride-1 IResNet100 layer3 blocks
