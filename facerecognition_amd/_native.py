@@ -98,6 +98,12 @@ _SIGS = {
     "fr_match_eval": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
                               c_void_p, c_int, ctypes.c_float, ctypes.c_float, c_void_p]),
     "fr_debug_match_eval_splits": (c_int, [c_void_p, c_int]),
+    "fr_match_range_workspace": (c_size_t, [c_void_p, c_int]),
+    "fr_match_range_count": (c_int, [c_void_p, c_void_p, c_int, ctypes.c_float, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "fr_match_range_fill": (c_int, [c_void_p, c_void_p, c_int, ctypes.c_float, c_void_p, c_void_p, c_void_p, c_void_p,
+                                    c_void_p, c_int64, c_void_p]),
+    "fr_debug_match_range_splits": (c_int, [c_void_p, c_int]),
+    "fr_gallery_read": (c_int, [c_void_p, c_int64, c_int64, c_void_p, c_int]),
     "fr_topk_merge": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]),
     "fr_topk_merge_ranks": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]),
     "fr_embed_match": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p,

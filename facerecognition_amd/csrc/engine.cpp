@@ -2289,6 +2289,84 @@ int fr_debug_match_eval_splits(fr_handle* h, int B) {
     return n_split;
 }
 
+size_t fr_match_range_workspace(const fr_handle* h, int B) {
+    if (!h || B <= 0) { set_error("fr_match_range_workspace: bad argument"); return 0; }
+    fr_handle* hm = const_cast<fr_handle*>(h);
+    std::lock_guard<std::mutex> lk(hm->mu);
+    if (!h->gallery || h->g_rows <= 0) { set_error("fr_match_range_workspace: no gallery"); return 0; }
+    const size_t n = match_range_workspace(B, h->g_rows, h->g_dim);
+    if (!n) set_error("fr_match_range_workspace: needs a gallery below 2^31 rows");
+    return n;
+}
+
+// The checks fr_match_range_count and fr_match_range_fill share, past their own pointer arguments.
+static int range_state_check(fr_handle* h, const char* who) {
+    if (!h->gallery || h->g_rows <= 0) { set_error(std::string(who) + ": no gallery"); return FR_ERR_STATE; }
+    if (h->g_rows > 0x7fffffff) { set_error(std::string(who) + ": needs a gallery below 2^31 rows"); return FR_ERR_ARG; }
+    return FR_OK;
+}
+
+int fr_match_range_count(fr_handle* h, const float* P, int B, float thresh, const int32_t* after, void* ws,
+                         int64_t* lims, void* stream) {
+    if (!P || !ws || !lims || B <= 0 || std::isnan(thresh)) {
+        set_error("fr_match_range_count: bad argument (P, ws, lims must be set, B >= 1, thresh not NaN)");
+        return FR_ERR_ARG;
+    }
+    if (!h) { set_error("fr_match_range_count: null handle"); return FR_ERR_ARG; }
+    std::lock_guard<std::mutex> lk(h->mu);
+    if (int rc = range_state_check(h, "fr_match_range_count")) return rc;
+    FR_HIP_CHECK(hipSetDevice(h->device));
+    FR_HIP_CHECK(launch_match_range_count(P, B, h->gallery, h->g_rows, h->g_dim, h->g_base, thresh, after, (int32_t*)ws,
+                                          lims, (hipStream_t)stream));
+    return FR_OK;
+}
+
+int fr_match_range_fill(fr_handle* h, const float* P, int B, float thresh, const int32_t* after, const void* ws,
+                        const int64_t* lims, float* scores, int32_t* idx, int64_t capacity, void* stream) {
+    if (!P || !ws || !lims || !scores || !idx || B <= 0 || std::isnan(thresh) || capacity < 0) {
+        set_error("fr_match_range_fill: bad argument (P, ws, lims, scores, idx must be set, B >= 1, thresh not NaN, "
+                  "capacity >= 0)");
+        return FR_ERR_ARG;
+    }
+    if (!h) { set_error("fr_match_range_fill: null handle"); return FR_ERR_ARG; }
+    std::lock_guard<std::mutex> lk(h->mu);
+    if (int rc = range_state_check(h, "fr_match_range_fill")) return rc;
+    FR_HIP_CHECK(hipSetDevice(h->device));
+    FR_HIP_CHECK(launch_match_range_fill(P, B, h->gallery, h->g_rows, h->g_dim, h->g_base, thresh, after,
+                                         (const int32_t*)ws, lims, scores, idx, capacity, (hipStream_t)stream));
+    return FR_OK;
+}
+
+int fr_debug_match_range_splits(fr_handle* h, int B) {
+    if (!h || B <= 0) { set_error("fr_debug_match_range_splits: bad argument"); return FR_ERR_ARG; }
+    std::lock_guard<std::mutex> lk(h->mu);
+    if (!h->gallery || h->g_rows <= 0) { set_error("fr_debug_match_range_splits: no gallery"); return FR_ERR_STATE; }
+    int n_split;
+    int64_t rps;
+    match_range_plan(B, h->g_rows, h->g_dim, &n_split, &rps);
+    return n_split;
+}
+
+int fr_gallery_read(const fr_handle* h, int64_t row0, int64_t n, float* out, int out_on_device) {
+    if (row0 < 0 || n < 0 || (!out && n > 0)) {
+        set_error("fr_gallery_read: bad argument (row0 >= 0, n >= 0, out must be set)");
+        return FR_ERR_ARG;
+    }
+    if (!h) { set_error("fr_gallery_read: null handle"); return FR_ERR_ARG; }
+    fr_handle* hm = const_cast<fr_handle*>(h);
+    std::lock_guard<std::mutex> lk(hm->mu);
+    if (row0 > h->g_rows || n > h->g_rows - row0) {
+        set_error("fr_gallery_read: rows [" + std::to_string(row0) + ", " + std::to_string(row0) + " + " +
+                  std::to_string(n) + ") outside a gallery of " + std::to_string(h->g_rows) + " rows");
+        return FR_ERR_ARG;
+    }
+    if (n == 0) return FR_OK;
+    FR_HIP_CHECK(hipSetDevice(h->device));
+    FR_HIP_CHECK(hipMemcpy(out, h->gallery + (size_t)row0 * h->g_dim, (size_t)n * h->g_dim * sizeof(float),
+                           out_on_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost));
+    return FR_OK;
+}
+
 int fr_topk_merge(const float* cand_s, const int32_t* cand_i, int B, int n_lists, int k, float* scores,
                   int32_t* idx, void* stream) {
     if (!cand_s || !cand_i || !scores || !idx || B <= 0 || n_lists <= 0 || k <= 0 || k > 16) {

@@ -348,6 +348,16 @@ void match_eval_plan(int B, int64_t N, int D, int* n_split, int64_t* rows_per_sp
 hipError_t launch_match_eval(const float* P, int B, const float* G, int64_t N, int D, int64_t index_base,
                              const int32_t* true_idx, float* true_score, int32_t* true_rank,
                              unsigned long long* hist, int nbins, float lo, float inv_w, hipStream_t s);
+// Range search (match_range.hip): every pair with score >= thresh (and index_base + j > after[b] when `after` is
+// set) as a CSR list, each probe's hits in ascending index.  count: ws [n_split][B] int32 (match_range_workspace
+// bytes) and lims [B + 1]; fill: the same arguments again, positions >= capacity not written.  N < 2^31.
+void match_range_plan(int B, int64_t N, int D, int* n_split, int64_t* rows_per_split);
+size_t match_range_workspace(int B, int64_t N, int D);
+hipError_t launch_match_range_count(const float* P, int B, const float* G, int64_t N, int D, int64_t index_base,
+                                    float thresh, const int32_t* after, int32_t* ws, int64_t* lims, hipStream_t s);
+hipError_t launch_match_range_fill(const float* P, int B, const float* G, int64_t N, int D, int64_t index_base,
+                                   float thresh, const int32_t* after, const int32_t* ws, const int64_t* lims,
+                                   float* scores, int32_t* idx, int64_t capacity, hipStream_t s);
 hipError_t launch_segment_mean_normalize(const float* E, int D, const int32_t* seg_start, int n_seg,
                                          float* out, hipStream_t s);
 // Gallery preparation: rows with |‖g‖-1| >= 1e-3 divided by ‖g‖ (cosine_similarity semantics).

@@ -5,7 +5,8 @@ Drop-in for the reference's three match paths:
     ``sort(reverse=True)`` (inference/recognition_engine.py:267-289, :41-63);
   * FAISS ``IndexFlatIP`` (``build_faiss_index`` extract_embeddings.py:595-645, searched in
     recognition_engine.py:291-326) — ``DeviceGallery`` exposes the same ``add``/``search``/
-    ``ntotal`` surface, ``search`` returning (scores, ids) with ids int64 and -1 padding;
+    ``ntotal`` surface, ``search`` returning (scores, ids) with ids int64 and -1 padding, plus
+    ``range_search`` (score >= thresh, the reference's rule, where faiss is strict) and ``reconstruct_n``;
   * the notebook's batched ``np.dot(emb, P.T)`` + ``argmax``/``argsort[:, -5:]``.
 Order is (score desc, index asc) everywhere, i.e. ``np.argmax``'s first-max rule and the
 stable sort's insertion order on ties.
@@ -183,6 +184,107 @@ class DeviceGallery:
         return {"scores": cat("scores", np.float32), "idx": cat("idx", np.int64),
                 "true_score": cat("true_score", np.float32), "true_rank": cat("true_rank", np.int64),
                 "hist": None if hist is None else hist.cpu().numpy()}
+
+    def range_search_device(self, probes_dev, thresh: float, after=None):
+        """Every gallery row scoring >= thresh per probe (fr_match_range_count / _fill): probes_dev cuda f32
+        [B, D]; ``after`` None or int32 [B] of global indices (probe b keeps only rows with index >
+        after[b]).  Returns device tensors ``(lims int64 [B + 1], scores f32 [T], idx int32 [T])``: probe b's
+        hits are ``[lims[b], lims[b + 1])``, in ascending index.  Reading the total ``lims[-1]`` to size the
+        output is the one synchronisation.  Note faiss's range_search is strict (>); this is >=, the
+        reference's known-iff-not-below-threshold rule."""
+        import torch
+
+        p = probes_dev.float().contiguous()
+        B = int(p.shape[0])
+        if B == 0 or self.ntotal == 0:
+            return (torch.zeros((B + 1,), dtype=torch.int64, device=self.device),
+                    torch.empty((0,), dtype=torch.float32, device=self.device),
+                    torch.empty((0,), dtype=torch.int32, device=self.device))
+        a = None
+        if after is not None:
+            a = after.to(device=self.device, dtype=torch.int32).contiguous()
+            if tuple(a.shape) != (B,):
+                raise ValueError(f"range_search_device: after must be [{B}]")
+        L = N.lib()
+        ws_bytes = int(L.fr_match_range_workspace(self._h, B))
+        if ws_bytes <= 0:
+            N.check(-1, "fr_match_range_workspace")
+        ws = torch.empty(((ws_bytes + 3) // 4,), dtype=torch.int32, device=self.device)
+        lims = torch.empty((B + 1,), dtype=torch.int64, device=self.device)
+        st = N.stream_ptr(self.device)
+        N.check(L.fr_match_range_count(self._h, N.ptr(p), B, float(thresh), N.ptr(a), N.ptr(ws), N.ptr(lims), st),
+                "fr_match_range_count")
+        total = int(lims[-1].item())
+        s = torch.empty((total,), dtype=torch.float32, device=self.device)
+        i = torch.empty((total,), dtype=torch.int32, device=self.device)
+        if total:
+            N.check(L.fr_match_range_fill(self._h, N.ptr(p), B, float(thresh), N.ptr(a), N.ptr(ws), N.ptr(lims),
+                                          N.ptr(s), N.ptr(i), total, st), "fr_match_range_fill")
+        return lims, s, i
+
+    def range_search(self, probes, thresh: float, order: str = "index", chunk: int = 8192,
+                     max_hits: Optional[int] = None) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+        """IndexFlatIP.range_search with >= instead of faiss's >: numpy ``(lims int64 [B + 1], D f32 [T],
+        I int64 [T])``.  ``order="index"`` leaves each probe's hits in ascending index, ``"score"`` puts
+        them in the match order (score descending, index ascending).  Probes go to the device ``chunk``
+        rows at a time; RuntimeError once the total passes ``max_hits``."""
+        import torch
+
+        if order not in ("index", "score"):
+            raise ValueError("range_search: order is 'index' or 'score'")
+        p = torch.as_tensor(np.asarray(probes, dtype=np.float32) if not torch.is_tensor(probes) else probes)
+        p = p.reshape(-1, self.d)
+        B = int(p.shape[0])
+        lims = np.zeros(B + 1, np.int64)
+        if B == 0 or self.ntotal == 0:
+            return lims, np.zeros(0, np.float32), np.zeros(0, np.int64)
+        D_parts, I_parts, total = [], [], 0
+        for b0 in range(0, B, chunk):
+            l, s, i = self.range_search_device(p[b0:b0 + chunk].to(self.device), thresh)
+            nb = int(l.shape[0]) - 1
+            if order == "score" and int(s.shape[0]):
+                seg = torch.repeat_interleave(torch.arange(nb, device=self.device), l[1:] - l[:-1])
+                o1 = torch.sort(s, descending=True, stable=True)[1]  # ties keep ascending index
+                o = o1[torch.sort(seg[o1], stable=True)[1]]
+                s, i = s[o], i[o]
+            lims[b0 + 1:b0 + nb + 1] = total + l[1:].cpu().numpy()
+            total = int(lims[b0 + nb])
+            if max_hits is not None and total > max_hits:
+                raise RuntimeError(f"range_search: more than max_hits = {max_hits} hits")
+            D_parts.append(s.cpu().numpy())
+            I_parts.append(i.cpu().numpy().astype(np.int64))
+        return lims, np.concatenate(D_parts), np.concatenate(I_parts)
+
+    def reconstruct_n(self, row0: int = 0, n: Optional[int] = None, device: bool = False):
+        """IndexFlatIP.reconstruct_n: the stored rows [row0, row0 + n) (local row numbers) as the match uses
+        them, i.e. divided by their norm where it differed from 1 by >= 1e-3 (fr_gallery_read).  numpy
+        [n, D] f32, or a device tensor with ``device=True``."""
+        import torch
+
+        n = self.ntotal - row0 if n is None else n
+        if row0 < 0 or n < 0 or row0 + n > self.ntotal:
+            raise IndexError(f"rows [{row0}, {row0 + n}) outside a {self.ntotal}-row gallery")
+        out = torch.empty((n, self.d), dtype=torch.float32, device=self.device if device else "cpu")
+        if n:
+            N.check(N.lib().fr_gallery_read(self._h, int(row0), int(n), N.ptr(out), int(device)), "fr_gallery_read")
+        return out if device else out.numpy()
+
+    def self_pairs(self, thresh: float, chunk: int = 4096) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+        """Every pair of gallery rows i < j with score >= thresh: numpy ``(i int64, j int64, score f32)`` in
+        (i, j) ascending order, indices global.  The stored rows are read back on the device ``chunk`` at a
+        time and searched as probes with ``after`` = their own index, so no N x N matrix exists anywhere
+        (duplicate or mislabelled prototypes of a DatabaseBuilder gallery)."""
+        import torch
+
+        ii, jj, ss = [np.zeros(0, np.int64)], [np.zeros(0, np.int64)], [np.zeros(0, np.float32)]
+        for r0 in range(0, self.ntotal, chunk):
+            m = min(chunk, self.ntotal - r0)
+            own = torch.arange(r0, r0 + m, device=self.device, dtype=torch.int64) + self.index_base
+            l, s, j = self.range_search_device(self.reconstruct_n(r0, m, device=True), thresh, own.to(torch.int32))
+            ii.append(torch.repeat_interleave(own, l[1:] - l[:-1]).cpu().numpy())
+            jj.append(j.cpu().numpy().astype(np.int64))
+            ss.append(s.cpu().numpy())
+        return np.concatenate(ii), np.concatenate(jj), np.concatenate(ss)
 
     def close(self) -> None:
         if self._own and getattr(self, "_h", None):

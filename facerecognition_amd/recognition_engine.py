@@ -420,14 +420,18 @@ class RecognitionEngine:
             S[sel], I[sel] = self._merge(lists, k) if len(lists) > 1 else lists[0]
         sel = np.nonzero(~p_on)[0]
         if len(sel):  # other probes (zero probes stay zero: every score 0.0): dot / (|p| |g|) everywhere
-            if "all" not in parts:
-                from .gallery import DeviceGallery
-                rows = np.stack([np.asarray(self._db[nm], dtype=np.float32).reshape(-1) for nm in names])
-                nr = np.linalg.norm(rows, axis=1)
-                parts["all"] = (DeviceGallery(rows / np.where(nr > 0, nr, 1.0)[:, None], dim=parts["dim"],
-                                              device=parts["dev"]), _Grow(np.arange(len(names))))
-            S[sel], I[sel] = self._search_mapped(parts["all"], E_unit[sel], k)
+            S[sel], I[sel] = self._search_mapped(self._db_all_part(parts, names), E_unit[sel], k)
         return S, I, names
+
+    def _db_all_part(self, parts, names):
+        """The 'all' copy of the dict db (every row divided by its norm), built on first use."""
+        if "all" not in parts:
+            from .gallery import DeviceGallery
+            rows = np.stack([np.asarray(self._db[nm], dtype=np.float32).reshape(-1) for nm in names])
+            nr = np.linalg.norm(rows, axis=1)
+            parts["all"] = (DeviceGallery(rows / np.where(nr > 0, nr, 1.0)[:, None], dim=parts["dim"],
+                                          device=parts["dev"]), _Grow(np.arange(len(names))))
+        return parts["all"]
 
     def _result_db(self, s_row, i_row, names):
         top = [(names[j], float(v)) for v, j in zip(s_row, i_row)]
@@ -441,6 +445,57 @@ class RecognitionEngine:
             return "No database", 0.0, []
         s, i, names = self._db_topk(np.asarray(embedding)[None], 5)
         return self._result_db(s[0], i[0], names)
+
+    @staticmethod
+    def _f32_threshold(t: float) -> float:
+        """The smallest float32 >= t: for a float32 score s, s >= that value iff not s < t."""
+        tf = np.float32(t)
+        if float(tf) < t:
+            tf = np.nextafter(tf, np.float32(np.inf))
+        return float(tf)
+
+    def recognize_all_with_db(self, embedding: np.ndarray, threshold: float = None) -> List[Tuple[str, float]]:
+        """Every db identity the decision rule accepts (not score < threshold; default self.threshold), in
+        (score descending, insertion order) order -- a watch-list query.  Its first entry is
+        recognize_with_db's (identity, score) whenever that is not "Unknown", and the list is empty exactly
+        when it is.  Scores follow cosine_similarity's rule per pair (see _db_gallery).  [] with no database."""
+        if self.db is None or len(self._db) == 0:
+            return []
+        t = self._f32_threshold(self.threshold if threshold is None else threshold)
+        parts, names = self._db_gallery()
+        e = np.asarray(embedding, dtype=np.float32).reshape(1, -1)
+        ne = float(np.linalg.norm(e))
+        unit = e / (ne if ne > 0 else 1.0)
+        if abs(ne - 1.0) < 1e-3:
+            searches = [(parts["on"], e), (parts["off"], unit)]
+        else:
+            searches = [(self._db_all_part(parts, names), unit)]
+        S, R = [np.zeros(0, np.float32)], [np.zeros(0, np.int64)]
+        for part, p in searches:
+            if part is None:
+                continue
+            g, idx = part
+            _, s, i = g.range_search(p, t)
+            S.append(s)
+            R.append(np.asarray(idx.view)[i])
+        s, r = np.concatenate(S), np.concatenate(R)
+        order = np.lexsort((r, -s))
+        return [(names[int(r[o])], float(s[o])) for o in order]
+
+    def find_duplicate_identities(self, threshold: float) -> List[Tuple[str, str, float]]:
+        """Pairs of db identities whose prototypes score >= threshold (two folders of one person, a
+        mislabelled folder), as (earlier name, later name, score) sorted by score descending: the device
+        self-join of DeviceGallery.self_pairs, no N x N matrix.  A db of unit-norm rows is scored as it
+        is; one with other rows on the copy with every row divided by its norm (cosine)."""
+        if self.db is None or len(self._db) < 2:
+            return []
+        parts, names = self._db_gallery()
+        g, idx = parts["on"] if parts["off"] is None else self._db_all_part(parts, names)
+        i, j, s = g.self_pairs(self._f32_threshold(threshold))
+        rows = np.asarray(idx.view)
+        ri, rj = rows[i], rows[j]
+        order = np.lexsort((rj, ri, -s))
+        return [(names[int(ri[o])], names[int(rj[o])], float(s[o])) for o in order]
 
     def _faiss_topk(self, E: np.ndarray, k: int):
         import torch

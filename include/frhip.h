@@ -177,6 +177,43 @@ int fr_match_eval(fr_handle* h, const float* P, int B, const int32_t* true_idx, 
                   float* scores, int32_t* idx, float* true_score, int32_t* true_rank,
                   uint64_t* hist, int nbins, float lo, float hi, void* stream);
 
+/* Threshold (range) search of P [B, D] (device f32) against the gallery: every gallery row whose score is
+ * >= thresh, without the B x N score matrix and without a guessed k.  This is the reference's decision rule
+ * as a query -- an identity is known iff not best_score < threshold (recognition_engine.py:286,323) -- and
+ * the IndexFlatIP.range_search member of the surface fr_match_topk serves; NOTE faiss's own range_search
+ * keeps score > radius (strict), this keeps score >= thresh.  Scores are the bits the exact f32 match path
+ * (fr_match_topk) gives each pair.  The result is a CSR list in two stream-ordered calls with no host
+ * synchronisation inside:
+ *   fr_match_range_count  writes lims [B + 1] int64 (device): lims[b] = number of hits of probes < b,
+ *                         lims[B] = the total; and fills the workspace ws (device,
+ *                         fr_match_range_workspace(h, B) bytes, need not be zeroed);
+ *   fr_match_range_fill   writes scores [.] f32 and idx [.] int32 (device): probe b's hits are positions
+ *                         lims[b] .. lims[b + 1] - 1 in ascending gallery index (global: index_base
+ *                         included), the same order in every run (no atomics, no sort).  Positions
+ *                         >= capacity are not written, so capacity < lims[B] truncates the list at its end
+ *                         (the caller sees it by reading lims[B]).
+ * fill must be given the same P, B, thresh, after and ws as the count that produced lims, with the gallery
+ * unchanged (no fr_gallery_set / fr_gallery_write) between the two calls; anything else is undefined.
+ * after (NULL: none) is [B] int32 (device) of global indices: probe b keeps only rows with index >
+ * after[b].  With the gallery's own rows as probes (fr_gallery_read) and after[b] = the probe's own global
+ * index this is the self-join "all pairs i < j with score >= thresh", each pair once.
+ * thresh = -INFINITY keeps every row (a NaN score is never kept); a NaN thresh is FR_ERR_ARG.  N < 2^31.
+ * Null or bad arguments: FR_ERR_ARG; no gallery: FR_ERR_STATE.  fr_match_range_workspace returns 0 on error
+ * (null handle, B <= 0, no gallery); its value depends on B and on the gallery's rows and dimension. */
+size_t fr_match_range_workspace(const fr_handle* h, int B);
+int fr_match_range_count(fr_handle* h, const float* P, int B, float thresh, const int32_t* after,
+                         void* ws, int64_t* lims, void* stream);
+int fr_match_range_fill(fr_handle* h, const float* P, int B, float thresh, const int32_t* after,
+                        const void* ws, const int64_t* lims, float* scores, int32_t* idx,
+                        int64_t capacity, void* stream);
+
+/* Copy the stored gallery rows [row0, row0 + n) (local row numbers, as in fr_gallery_write) to out [n, D]
+ * f32 in host or device memory: the prepared rows the match uses (divided by their norm where
+ * fr_gallery_set's rule says so).  IndexFlatIP.reconstruct_n; also the self-join's probes without a host
+ * copy of the gallery.  n = 0 copies nothing; n < 0 or a range outside the gallery is FR_ERR_ARG.
+ * Synchronous. */
+int fr_gallery_read(const fr_handle* h, int64_t row0, int64_t n, float* out, int out_on_device);
+
 /* Merge n_lists candidate lists per probe: cand_s/cand_i [B, n_lists, k] → [B, k]
  * with the same (score desc, index asc) order.  Used after the RCCL all-gather of
  * per-shard candidates. */
@@ -450,6 +487,8 @@ int fr_get_option(const fr_handle* h, int option);
 int fr_debug_match_fallbacks(fr_handle* h);
 /* Number of gallery splits fr_match_eval's main pass takes for a batch of B probes (no device work). */
 int fr_debug_match_eval_splits(fr_handle* h, int B);
+/* The same for fr_match_range_count / fr_match_range_fill (the second dimension of their workspace). */
+int fr_debug_match_range_splits(fr_handle* h, int B);
 /* Number of bounded waits of the split stage kernels (layer2: two workgroups per image, layer1: four,
  * exchanging boundary rows per conv) that ran out before the partner published; 0 on a healthy device
  * (synchronizes the device).  Each one was either re-run (fr_embed's default) or reported as
