@@ -23,10 +23,16 @@ def __getattr__(name):  # lazy: importing the package must not initialise the GP
     if name in _EXPLAIN:
         from . import explainability
         return getattr(explainability, name)
+    if name in _LBPH:
+        from . import lbph
+        return getattr(lbph, name)
     raise AttributeError(name)
 
 
 _EXPLAIN = ("ExplainabilityEngine", "FaceNetExplainabilityEngine", "generate_heatmap", "overlay_heatmap",
             "explain_prediction", "cam_closed_form")
+_LBPH = ("LBPHFaceRecognizer", "LBPHFaceRecognizer_create", "train_lbph_model", "recognize_face",
+         "find_optimal_threshold", "create_label_map_from_directory", "load_faces_and_labels",
+         "train_lbph_from_directory")
 _EVALUATE = ("compute_metrics", "threshold_sweep", "roc_analysis", "generate_report", "evaluate_recognition_engine",
              "closed_set_report", "evaluate_closed_set")

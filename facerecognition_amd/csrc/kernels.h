@@ -382,4 +382,20 @@ hipError_t launch_mtcnn_head(const float* x, int64_t M, int C, const float* w, c
                              hipStream_t s);
 int pool_ceil_out(int H, int k, int s);
 
+// LBPH (lbph.hip): extended-LBP cell histograms as u16 counts, chi-square top-k on counts (DESIGN.md §4 LBPH).
+// The neighbour table comes from the host (lbph_table, lbph.cpp): per neighbour {fx, fy, cx, cy} and {w1..w4}.
+struct LbphTable {
+    int32_t off[8][4];
+    float w[8][4];
+};
+void lbph_table(int radius, int neighbors, LbphTable* t);
+// img [B][H][W] u8 -> counts [B][grid_y * grid_x * 2^neighbors] u16 (4-byte aligned); arguments already checked.
+hipError_t launch_lbph_hist(const uint8_t* img, int B, int H, int W, int radius, int neighbors, int grid_x, int grid_y,
+                            const LbphTable& tab, uint16_t* counts, hipStream_t s);
+// The k smallest 2 / P * sum (ka - kb)^2 / (ka + kb) per probe, ascending, equal distances by ascending index;
+// dist [B][k] f64, idx [B][k] (+inf / -1 past N).  ws: lbph_match_workspace bytes.  B <= 65535, k <= 32, N <= 2^30.
+size_t lbph_match_workspace(int B, int64_t N, int k);
+hipError_t launch_lbph_match(const uint16_t* Q, int B, const uint16_t* G, int64_t N, int D, int cell_pixels, int k,
+                             double* dist, int32_t* idx, void* ws, hipStream_t s);
+
 }  // namespace fr

@@ -10,11 +10,14 @@ the GPU instead of one forward per image.
 Differences, by design:
   * ``config["device"]`` defaults to ``"cuda"`` (the reference defaults to ``"cpu"``,
     database_builder.py:197,224); this package has no CPU compute path.
-  * ``model_type == "lbph"`` (OpenCV LBPH training, :141-182) is outside the embedding hot path and
-    fails the job with a clear message (out of scope).
+  * ``model_type == "lbph"`` (:140-182) trains the device LBPH recognizer (``lbph.train_lbph_from_directory``:
+    histogram extraction in one ``fr_lbph_hist``) with the reference's config keys and defaults.  The model file
+    is ``.npz``, not OpenCV's XML: a ``model_name`` with another extension (the reference's default
+    ``lbph_model.xml``) has it replaced, and a log line says so.  No config file is rewritten.
 """
 from __future__ import annotations
 
+import os
 import threading
 import traceback
 from datetime import datetime
@@ -106,17 +109,39 @@ class DatabaseBuilder:
             job.set_status("running")
             job.update_progress(5, "Đang khởi tạo build process...")
             if job.model_type == "lbph":
-                raise NotImplementedError("LBPH training is out of scope for facerecognition_amd "
-                                          "(OpenCV LBPH, not on the embedding hot path)")
-            if job.model_type not in ("arcface", "facenet"):
+                self._build_lbph(job)
+            elif job.model_type in ("arcface", "facenet"):
+                self._build_embeddings(job)
+            else:
                 raise ValueError(f"Model type không hợp lệ: {job.model_type}")
-            self._build_embeddings(job)
             job.update_progress(100, "Hoàn thành!")
             job.set_status("completed")
         except Exception as e:  # reference :135-138
             job.set_error(str(e))
             job.add_log(traceback.format_exc())
             job.set_status("failed")
+
+    def _build_lbph(self, job: BuildJob):
+        """Reference :140-182: same config keys, defaults and progress messages; the output entry is the model
+        file alone (label_map.npy and optimal_threshold.txt are written beside it)."""
+        from .lbph import npz_model_name, train_lbph_from_directory
+        job.update_progress(10, "Đang load LBPH config...")
+        cfg = job.config
+        data_dir = cfg.get("data_dir")
+        output_dir = cfg.get("output_dir", "models/checkpoints/LBHP")
+        model_name = cfg.get("model_name", "lbph_model.xml")
+        if npz_model_name(model_name) != model_name:
+            job.add_log(f"LBPH model file is .npz (OpenCV XML/YAML is not written): {model_name} -> "
+                        f"{npz_model_name(model_name)}")
+            model_name = npz_model_name(model_name)
+        job.update_progress(20, f"Đang train LBPH từ {data_dir}...")
+        train_lbph_from_directory(
+            data_dir=data_dir, output_dir=output_dir, model_name=model_name, radius=cfg.get("radius", 1),
+            neighbors=cfg.get("neighbors", 8), grid_x=cfg.get("grid_x", 8), grid_y=cfg.get("grid_y", 8),
+            use_val_for_threshold=cfg.get("find_threshold", False), val_dir=cfg.get("val_dir"),
+            use_face_detection=cfg.get("use_face_detection", True),
+            target_size=tuple(cfg.get("target_size", [100, 100])))
+        job.add_output_file("LBPH Model", os.path.join(output_dir, model_name))
 
     def _build_embeddings(self, job: BuildJob):
         mt = job.model_type

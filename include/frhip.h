@@ -287,6 +287,34 @@ int fr_mtcnn_head(const float* x, int64_t M, int C, const float* w, const float*
 int fr_nms_host(const float* boxes, int64_t n, const int64_t* order, float thresh, int min_mode, int64_t* keep,
                 int64_t* n_keep);
 
+/* ---- LBPH (the models/lbphmodel package, cv2.face.LBPHFaceRecognizer): OpenCV's published algorithm restated, handle-free.
+ *      Checked against a float32/float64 numpy restatement (tests/lbph_ref.py), not against a cv2.face build.
+ *      A histogram is kept as u16 counts [D], D = grid_x * grid_y * 2^neighbors, cells row-major; OpenCV's float32
+ *      histogram is count / (float)P, P = cw * ch pixels per cell, cw = (W - 2 radius) / grid_x,
+ *      ch = (H - 2 radius) / grid_y (integer division; pixels past grid * cell are ignored). ---- */
+
+/* The extended-LBP neighbour table (host only): for neighbour n, offs[n] = {fx, fy, cx, cy} and
+ * w[n] = {w1, w2, w3, w4}, float32 as OpenCV computes them.  radius 1..4, neighbors 1..8, else FR_ERR_ARG. */
+int fr_lbph_table(int radius, int neighbors, int32_t* offs /*[n][4]*/, float* w /*[n][4]*/);
+/* img (device u8) [B][H][W] gray -> counts (device u16, 4-byte aligned) [B][D].  Bit n of a pixel's code is set when
+ * the float32 bilinear sample t = w1 a + w2 b + w3 c + w4 d (each product rounded, summed left to right, no fused
+ * multiply-add) has t > centre or |t - centre| < FLT_EPSILON.  Supported: radius 1..4, neighbors 1..8, grid_x and
+ * grid_y 1..16, H and W <= 512, cw >= 1, ch >= 1, P <= 65535, B 1..2^24; anything else is FR_ERR_ARG, decided
+ * before any HIP call. */
+int fr_lbph_hist(const uint8_t* img, int B, int H, int W, int radius, int neighbors, int grid_x, int grid_y,
+                 uint16_t* counts, void* stream);
+/* Bytes of device workspace fr_lbph_match needs (0 and a message on bad arguments). */
+size_t fr_lbph_match_workspace(int B, int64_t N, int D, int k);
+/* HISTCMP_CHISQR_ALT top-k: for each of B probe count rows Q [B][D] the k smallest
+ * d = 2 * sum_j (a_j - b_j)^2 / (a_j + b_j) over the gallery count rows G [N][D] (a = count / P; bins with
+ * a_j + b_j = 0 skipped), ascending, equal distances by ascending row; dist (device f64) [B][k], idx (device i32)
+ * [B][k], +inf / -1 past N.  Computed on the counts: each term (ka - kb)^2 / (ka + kb) in float32 with IEEE
+ * division, summed in float64 in an order that depends on D alone, times 2 / P: a probe's result is bitwise the
+ * same alone and in a batch.  No B x N matrix is written.  B 1..65535, N 1..2^30, D 1..65536, cell_pixels (P)
+ * 1..65535, k 1..32, else FR_ERR_ARG. */
+int fr_lbph_match(const uint16_t* Q, int B, const uint16_t* G, int64_t N, int D, int cell_pixels, int k, double* dist,
+                  int32_t* idx, void* ws, size_t ws_bytes, void* stream);
+
 /* ---- op-level entry points (kernel parity tests and custom graphs) ---- */
 
 /* Implicit-GEMM convolution on NHWC bf16 with fused epilogue:
