@@ -26,6 +26,9 @@ def __getattr__(name):  # lazy: importing the package must not initialise the GP
     if name in _LBPH:
         from . import lbph
         return getattr(lbph, name)
+    if name == "TSNE":
+        from .tsne import TSNE
+        return TSNE
     raise AttributeError(name)
 
 

@@ -148,6 +148,16 @@ _SIGS = {
     "fr_lbph_match_workspace": (c_size_t, [c_int, c_int64, c_int, c_int]),
     "fr_lbph_match": (c_int, [c_void_p, c_int, c_void_p, c_int64, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p,
                               c_size_t, c_void_p]),
+    "fr_tsne_knn_sqdist": (c_int, [c_void_p, c_int, c_int, c_void_p, c_int, c_void_p, c_void_p]),
+    "fr_tsne_affinities_workspace": (c_size_t, [c_int, c_int]),
+    "fr_tsne_affinities": (c_int, [c_void_p, c_void_p, c_int, c_int, ctypes.c_float, c_void_p, c_void_p, c_void_p,
+                                   c_void_p, c_void_p, c_size_t, c_void_p]),
+    "fr_tsne_gradient_workspace": (c_size_t, [c_int]),
+    "fr_tsne_gradient": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p, ctypes.c_float, c_void_p, c_void_p,
+                                 c_void_p, c_size_t, c_void_p]),
+    "fr_tsne_run": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, ctypes.c_float,
+                            ctypes.c_float, ctypes.c_float, c_int, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "fr_op_tsne_repulsion": (c_int, [c_void_p, c_int, c_void_p, c_size_t, c_void_p]),
     "fr_op_preprocess": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_int, c_void_p]),
     "fr_op_maxpool": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p,
                               c_int, c_int, c_int, c_int, c_int, c_void_p]),

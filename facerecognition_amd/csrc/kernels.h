@@ -398,4 +398,23 @@ size_t lbph_match_workspace(int B, int64_t N, int k);
 hipError_t launch_lbph_match(const uint16_t* Q, int B, const uint16_t* G, int64_t N, int D, int cell_pixels, int k,
                              double* dist, int32_t* idx, void* ws, hipStream_t s);
 
+// t-SNE (tsne.hip): sparse kNN affinities, exact pairwise repulsion, sklearn's optimiser step (DESIGN.md §4 t-SNE).
+// Arguments are checked by tsne_api.cpp; every launcher only enqueues on s.
+// d2 [N][k] = sum_d (X[i][d] - X[idx[i][j]][d])^2, by direct subtraction.
+hipError_t launch_tsne_knn_sqdist(const float* X, int N, int D, const int32_t* idx, int k, float* d2, hipStream_t s);
+// Bandwidth search per row + P = (P_cond + P_cond^T) / (2 N) as CSR with ascending columns; indptr [N + 1],
+// col / val [2 N k] (the first indptr[N] entries written), beta [N].  ws: tsne_affinities_workspace bytes.
+size_t tsne_affinities_workspace(int N, int k);
+hipError_t launch_tsne_affinities(const int32_t* idx, const float* d2, int N, int k, float perplexity, int32_t* indptr,
+                                  int32_t* col, float* val, float* beta, void* ws, hipStream_t s);
+// n_steps == 0: grad [N][2] and stats {KL, Z, |grad|} of Y.  n_steps >= 1: that many optimiser steps on Y / update /
+// gains in place; grad and stats are the last step's (its gradient is evaluated before its update).
+// ws: tsne_gradient_workspace bytes.
+size_t tsne_gradient_workspace(int N);
+// The repulsion launch alone, partials into ws (timing).
+hipError_t launch_tsne_repulsion(const float* Y, int N, void* ws, hipStream_t s);
+hipError_t launch_tsne_steps(const int32_t* indptr, const int32_t* col, const float* val, int N, float* Y,
+                             float* update, float* gains, float exaggeration, float momentum, float learning_rate,
+                             int n_steps, float* grad, double* stats, void* ws, hipStream_t s);
+
 }  // namespace fr

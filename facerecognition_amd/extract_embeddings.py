@@ -18,8 +18,8 @@ Reference → here:
   build_db :765-835, extract_embeddings_from_csv :446-552, full_pipeline :838-888
   FacePreprocessor / FaceNetPreprocessor :188-345   device MTCNN + device alignment warp (face_detector.py,
                                  SURVEY.md §8f row 4); without MTCNN weights the raw image is used, as the
-                                 reference does when its detector is unavailable.  t-SNE plotting is out of
-                                 scope.
+                                 reference does when its detector is unavailable.
+  visualize_tsne :648-711        the device TSNE (tsne.py) in place of sklearn's Barnes-Hut run
 """
 from __future__ import annotations
 
@@ -368,8 +368,42 @@ def read_index(path: str):
     return DeviceGallery(rows, dim=rows.shape[1])
 
 
-def visualize_tsne(*_a, **_k):
-    raise NotImplementedError("t-SNE plotting is out of scope for facerecognition_amd (SURVEY.md §2.1 row 1)")
+def visualize_tsne(embeddings: np.ndarray, labels: np.ndarray, output_path: str, num_samples: Optional[int] = 2000,
+                   perplexity: int = 30):
+    """Reference :648-711 with the device TSNE (tsne.py) in place of sklearn's: the same subsample rule, print lines
+    and scatter plot.  num_samples=None lays out every row (the subsample only existed to speed sklearn up).
+    Returns the (n, 2) layout, where the reference returns nothing; without matplotlib the plot is skipped with the
+    reference's message."""
+    from . import tsne as _tsne
+
+    print("\n=== T-SNE VISUALIZATION ===")
+    embeddings, labels = np.asarray(embeddings), np.asarray(labels)
+    if num_samples is not None and len(embeddings) > num_samples:
+        indices = np.random.choice(len(embeddings), num_samples, replace=False)
+        embeddings = embeddings[indices]
+        labels = labels[indices]
+    print(f"Running t-SNE on {len(embeddings)} samples...")
+    embeddings_2d = _tsne.TSNE(n_components=2, random_state=42, perplexity=perplexity, n_iter=1000).fit_transform(
+        embeddings)
+    try:
+        import matplotlib
+        matplotlib.use("Agg")
+        import matplotlib.pyplot as plt
+    except ImportError:
+        print("Thieu sklearn/matplotlib. Chay: pip install scikit-learn matplotlib")
+        return embeddings_2d
+    plt.figure(figsize=(14, 12))
+    cmap = "tab20" if len(np.unique(labels)) <= 20 else "viridis"
+    scatter = plt.scatter(embeddings_2d[:, 0], embeddings_2d[:, 1], c=labels, cmap=cmap, alpha=0.6, s=15)
+    plt.colorbar(scatter, label="Identity")
+    plt.title(f"ArcFace Embedding Space (t-SNE)\n{len(np.unique(labels))} identities, {len(embeddings)} samples")
+    plt.xlabel("t-SNE dimension 1")
+    plt.ylabel("t-SNE dimension 2")
+    plt.tight_layout()
+    plt.savefig(output_path, dpi=150, bbox_inches="tight")
+    plt.close()
+    print(f"Saved t-SNE visualization: {output_path}")
+    return embeddings_2d
 
 
 # ---------------------------------------------------------------------------------------- drivers
@@ -461,7 +495,7 @@ def full_pipeline(model_path: str, csv_path: str, data_root: str = None, output_
     prototypes = compute_prototypes(result["embeddings"], result["labels"],
                                     os.path.join(output_dir, "arcface_prototypes.npy"))
     build_faiss_index(prototypes, os.path.join(output_dir, "arcface_index.faiss"))
-    print("t-SNE visualization skipped (out of scope)")
+    visualize_tsne(result["embeddings"], result["labels"], os.path.join(output_dir, "tsne_visualization.png"))
     return result
 
 

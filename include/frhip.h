@@ -315,6 +315,47 @@ size_t fr_lbph_match_workspace(int B, int64_t N, int D, int k);
 int fr_lbph_match(const uint16_t* Q, int B, const uint16_t* G, int64_t N, int D, int cell_pixels, int k, double* dist,
                   int32_t* idx, void* ws, size_t ws_bytes, void* stream);
 
+/* ---- t-SNE (inference/extract_embeddings.py visualize_tsne, sklearn.manifold.TSNE's defaults): sparse kNN input
+ *      affinities as in sklearn's Barnes-Hut path, the repulsive term summed exactly over all pairs (angle 0), two
+ *      components.  Handle-free, caller-owned device buffers.  Common limits, each FR_ERR_ARG with a message before
+ *      any HIP call: non-null pointers, N >= 2, 1 <= k < N, k <= 4095, 2 N k < 2^31.  Every result is bitwise
+ *      repeatable: sums run in a fixed order and no floating-point atomics are used. ---- */
+
+/* d2 (device f32) [N][k] = sum_d (X[i][d] - X[idx[i][j]][d])^2 for X (device f32) [N][D], idx (device i32) [N][k]
+ * with entries in [0, N) (not checked), by direct subtraction in float32.  D >= 1. */
+int fr_tsne_knn_sqdist(const float* X, int N, int D, const int32_t* idx, int k, float* d2, void* stream);
+/* Bytes of device workspace fr_tsne_affinities needs (0 and a message on bad arguments). */
+size_t fr_tsne_affinities_workspace(int N, int k);
+/* Per row i the bandwidth beta[i] whose conditional p_j|i = exp(-beta d2[i][j]) / sum has entropy log(perplexity)
+ * (sklearn's _binary_search_perplexity: beta from 1, doubled or halved while unbounded, at most 100 steps, stop at
+ * |H - log perplexity| <= 1e-5; searched in float64 with each row's smallest distance subtracted first, which
+ * leaves p unchanged and keeps a far row from underflowing to zero), then P_ij = (p_j|i + p_i|j) / (2 N) as CSR
+ * with ascending columns: indptr (i32) [N + 1], col (i32) and val (f32) of capacity 2 N k each, of which the first
+ * indptr[N] are written.  A row's idx entries must be distinct and differ from the row's own index (not checked;
+ * repeated entries leave val unspecified but every write in bounds).  perplexity finite and > 0. */
+int fr_tsne_affinities(const int32_t* idx, const float* d2, int N, int k, float perplexity, int32_t* indptr,
+                       int32_t* col, float* val, float* beta, void* ws, size_t ws_bytes, void* stream);
+/* Bytes of device workspace fr_tsne_gradient and fr_tsne_run need (0 and a message on bad arguments). */
+size_t fr_tsne_gradient_workspace(int N);
+/* grad (f32) [N][2]: g_i = 4 (e sum_j P_ij w_ij (y_i - y_j) - sum_j w_ij^2 (y_i - y_j) / Z), w_ij = 1 / (1 + |y_i -
+ * y_j|^2), Z = sum_{i != j} w_ij, e = exaggeration; stats (device f64) [3] = {KL, Z, |grad|_2} with KL = sum_nnz
+ * P_ij (log P_ij + log(1 + |y_i - y_j|^2)) + log Z in float64 (entries with P_ij = 0 skipped; P without the
+ * exaggeration).  Pair terms in float32, each difference y_i - y_j formed before it is weighted.  The CSR's columns
+ * must lie in [0, N) (not checked).  exaggeration finite and > 0. */
+int fr_tsne_gradient(const int32_t* indptr, const int32_t* col, const float* val, int N, const float* Y,
+                     float exaggeration, float* grad, double* stats, void* ws, size_t ws_bytes, void* stream);
+/* n_steps (>= 1) steps of sklearn's _gradient_descent on Y, update, gains (f32 [N][2] each), in place and enqueued
+ * without host synchronisation: inc = update g < 0; gains += 0.2 where inc, *= 0.8 elsewhere, at least 0.01;
+ * update = momentum update - learning_rate gains g; Y += update.  grad and stats are those of the last step's
+ * gradient (evaluated before that step's update).  momentum and learning_rate finite and > 0. */
+int fr_tsne_run(const int32_t* indptr, const int32_t* col, const float* val, int N, float* Y, float* update,
+                float* gains, float exaggeration, float momentum, float learning_rate, int n_steps, float* grad,
+                double* stats, void* ws, size_t ws_bytes, void* stream);
+/* The repulsion launch of one iteration alone (timing): the per-split partials {sum w^2 dx, sum w^2 dy,
+ * sum_{j != i} w} of Y [N][2] go to the start of the workspace (fr_tsne_gradient_workspace bytes) as 16-byte records
+ * {fx, fy, z, 0}, and nothing else is written. */
+int fr_op_tsne_repulsion(const float* Y, int N, void* ws, size_t ws_bytes, void* stream);
+
 /* ---- op-level entry points (kernel parity tests and custom graphs) ---- */
 
 /* Implicit-GEMM convolution on NHWC bf16 with fused epilogue:
