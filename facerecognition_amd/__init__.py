@@ -29,9 +29,13 @@ def __getattr__(name):  # lazy: importing the package must not initialise the GP
     if name == "TSNE":
         from .tsne import TSNE
         return TSNE
+    if name in _ARCMARGIN:
+        from . import arcmargin
+        return getattr(arcmargin, name)
     raise AttributeError(name)
 
 
+_ARCMARGIN = ("ArcMarginProduct", "arcface_loss", "arcface_logits", "class_accuracy")
 _EXPLAIN = ("ExplainabilityEngine", "FaceNetExplainabilityEngine", "generate_heatmap", "overlay_heatmap",
             "explain_prediction", "cam_closed_form")
 _LBPH = ("LBPHFaceRecognizer", "LBPHFaceRecognizer_create", "train_lbph_model", "recognize_face",

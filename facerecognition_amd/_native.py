@@ -158,6 +158,14 @@ _SIGS = {
     "fr_tsne_run": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, ctypes.c_float,
                             ctypes.c_float, ctypes.c_float, c_int, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
     "fr_op_tsne_repulsion": (c_int, [c_void_p, c_int, c_void_p, c_size_t, c_void_p]),
+    "fr_arcmargin_workspace": (c_size_t, [c_int, c_int, c_int]),
+    "fr_arcmargin_forward": (c_int, [c_void_p, c_int, c_int, c_void_p, c_int, c_void_p, c_void_p, ctypes.c_float,
+                                     ctypes.c_float, ctypes.c_float, c_int, ctypes.c_float, c_void_p, c_void_p,
+                                     c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "fr_arcmargin_backward": (c_int, [c_void_p, c_int, c_int, c_void_p, c_int, c_void_p, c_void_p, ctypes.c_float,
+                                      ctypes.c_float, ctypes.c_float, c_int, ctypes.c_float, c_void_p, c_void_p,
+                                      c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t,
+                                      c_void_p]),
     "fr_op_preprocess": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_int, c_void_p]),
     "fr_op_maxpool": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p,
                               c_int, c_int, c_int, c_int, c_int, c_void_p]),

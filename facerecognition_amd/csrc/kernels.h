@@ -417,4 +417,32 @@ hipError_t launch_tsne_steps(const int32_t* indptr, const int32_t* col, const fl
                              float* update, float* gains, float exaggeration, float momentum, float learning_rate,
                              int n_steps, float* grad, double* stats, void* ws, hipStream_t s);
 
+// ArcFace margin-softmax loss (arcmargin.hip; DESIGN.md §4 "ArcFace margin loss").  Arguments are checked by
+// arcmargin_api.cpp; every launcher only enqueues on s.
+struct ArcArgs {
+    const float* E;  // [B][D] embeddings, not normalised
+    const float* W;  // [C][D] class centres, not normalised
+    int B, C, D;
+    const int32_t* label;    // [B]; outside [0, C): no margin, its loss term is 0
+    const int32_t* label_b;  // [B] mixup's second label, or null
+    float lam, scale, label_smoothing;
+    float cos_m, sin_m, th, mm;  // cos m, sin m, cos(pi - m), sin(pi - m) m
+    int easy_margin;
+    const float* inv_e;  // [B] 1 / max(|e_b|, 1e-12)
+    const float* inv_w;  // [C]
+    float* inv_e_out;    // forward: where the norms kernel writes them
+    float* inv_w_out;
+    float* loss;    // [B] (forward)
+    float* lse;     // [B] written by forward, read by backward
+    float* logits;  // [B][C] or null (forward)
+    const float* u;        // [B] upstream gradient per sample, or
+    const float* dlogits;  // [B][C] dense upstream gradient (backward; exactly one of the two)
+    int n_split;           // filled by the launchers (arcmargin_plan)
+    int64_t rows_per_split;
+};
+void arcmargin_plan(int B, int C, bool fwd, int* n_split, int64_t* rows_per_split);
+size_t arcmargin_workspace(int B, int C, int D);
+hipError_t launch_arcmargin_forward(ArcArgs a, void* ws, hipStream_t s);
+hipError_t launch_arcmargin_backward(ArcArgs a, float* dE, float* dW, void* ws, hipStream_t s);
+
 }  // namespace fr

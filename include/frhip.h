@@ -356,6 +356,41 @@ int fr_tsne_run(const int32_t* indptr, const int32_t* col, const float* val, int
  * {fx, fy, z, 0}, and nothing else is written. */
 int fr_op_tsne_repulsion(const float* Y, int N, void* ws, size_t ws_bytes, void* stream);
 
+/* ---- ArcFace margin loss (models/arcface/arcface_model.py ArcMarginProduct + nn.CrossEntropyLoss(label_smoothing)
+ *      + train_arcface.py's mixup criterion), forward and backward, without a B x C matrix.  Handle-free,
+ *      caller-owned device buffers; f32 and i32 device pointers, 16-byte aligned E, W, dE, dW.
+ *      With e^ = e / max(|e|, 1e-12), w^ likewise, c_bj = e^_b . w^_j (exact f32), s = scale, m = margin:
+ *        z_bj = s c_bj (j != y_b),  z_b,y = s zy,  q = 1 - c^2, sine = sqrt(max(q, 1e-7)), phi = c cos m - sine sin m,
+ *        zy = c > cos(pi - m) ? phi : c - sin(pi - m) m      (easy_margin: c > 0 ? phi : c)
+ *        CE(z, y) = (1 - ls)(lse - z_y) + ls (lse - mean_j z_j),  loss_b = lam CE(z_b, y_b) + (1 - lam) CE(z_b, y'_b)
+ *      (label_b NULL: lam = 1).  Only the first label gets the margin.  A label outside [0, C), in either array, is
+ *      defined: its CE term is 0 and gives no gradient, it never indexes memory, and an out-of-range first label
+ *      also means no margin for the row.
+ *      Limits, each FR_ERR_ARG with a message before any HIP call: B >= 1, C >= 2, D >= 4 and D % 4 == 0,
+ *      B C <= 2^40, C D <= 2^40, B D <= 2^40 (all indexing is 64-bit), scale finite and > 0, margin in [0, pi),
+ *      lam in [0, 1], label_smoothing in [0, 1), required pointers non-null, ws_bytes >= fr_arcmargin_workspace.
+ *      Every result is bitwise repeatable: sums run in an order fixed by (B, C, D), no floating-point atomics. ---- */
+
+/* Bytes of device workspace the two calls below need (0 and a message on bad arguments): the per-split partials
+ * of the log-sum-exp and of dE, a small multiple of B D floats -- never B C. */
+size_t fr_arcmargin_workspace(int B, int C, int D);
+/* loss [B], lse [B] = log sum_j exp z_bj, inv_e [B] = 1 / max(|e_b|, 1e-12), inv_w [C] (IEEE sqrt and division);
+ * logits [B][C] = z when non-NULL (ArcMarginProduct.forward's return value), else no B x C buffer exists. */
+int fr_arcmargin_forward(const float* E, int B, int D, const float* W, int C, const int32_t* label,
+                         const int32_t* label_b /*NULL*/, float lam, float scale, float margin, int easy_margin,
+                         float label_smoothing, float* loss, float* lse, float* inv_e, float* inv_w,
+                         float* logits /*NULL*/, void* ws, size_t ws_bytes, void* stream);
+/* dE [B][D] and / or dW [C][D] (at least one non-NULL) of sum_b u_b loss_b (u [B], with the forward's lse) or of a
+ * function of z with gradient dlogits [B][C] (lse may be NULL); exactly one of u and dlogits is non-NULL.  inv_e and
+ * inv_w are the forward's.  g_bj = u_b (softmax(z_b)_j - target_bj) s (j == y_b ? dzy/dc : 1) (or dlogits_bj in place
+ * of the first two factors), dE^ = g W^, dW^ = g^T E^, dE_b = (dE^_b - (dE^_b . e^_b) e^_b) / max(|e_b|, 1e-12), dW
+ * likewise; dzy/dc = cos m + (q >= 1e-7 ? sin m c / sine : 0) on the phi branch, 1 on the other. */
+int fr_arcmargin_backward(const float* E, int B, int D, const float* W, int C, const int32_t* label,
+                          const int32_t* label_b /*NULL*/, float lam, float scale, float margin, int easy_margin,
+                          float label_smoothing, const float* lse, const float* inv_e, const float* inv_w,
+                          const float* u /*NULL*/, const float* dlogits /*NULL*/, float* dE /*NULL*/,
+                          float* dW /*NULL*/, void* ws, size_t ws_bytes, void* stream);
+
 /* ---- op-level entry points (kernel parity tests and custom graphs) ---- */
 
 /* Implicit-GEMM convolution on NHWC bf16 with fused epilogue:
