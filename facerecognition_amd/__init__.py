@@ -32,10 +32,15 @@ def __getattr__(name):  # lazy: importing the package must not initialise the GP
     if name in _ARCMARGIN:
         from . import arcmargin
         return getattr(arcmargin, name)
+    if name in _TRIPLET:
+        from . import triplet
+        return getattr(triplet, name)
     raise AttributeError(name)
 
 
-_ARCMARGIN = ("ArcMarginProduct", "arcface_loss", "arcface_logits", "class_accuracy")
+_TRIPLET = ("TripletLoss", "mine_triplets", "mine_semi_hard_triplets", "mine_batch_hard_triplets", "triplet_loss",
+            "online_triplet_loss", "compute_triplet_metrics")
+_ARCMARGIN =("ArcMarginProduct", "arcface_loss", "arcface_logits", "class_accuracy")
 _EXPLAIN = ("ExplainabilityEngine", "FaceNetExplainabilityEngine", "generate_heatmap", "overlay_heatmap",
             "explain_prediction", "cam_closed_form")
 _LBPH = ("LBPHFaceRecognizer", "LBPHFaceRecognizer_create", "train_lbph_model", "recognize_face",

@@ -166,6 +166,14 @@ _SIGS = {
                                       ctypes.c_float, ctypes.c_float, c_int, ctypes.c_float, c_void_p, c_void_p,
                                       c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t,
                                       c_void_p]),
+    "fr_triplet_workspace": (c_size_t, [c_int, c_int]),
+    "fr_triplet_count": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p]),
+    "fr_triplet_mine": (c_int, [c_void_p, c_int, c_int, c_void_p, c_int, ctypes.c_float, c_void_p, c_void_p, c_void_p,
+                                c_void_p, c_int64, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "fr_triplet_loss_forward": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int64, ctypes.c_float,
+                                        c_void_p, c_void_p, c_void_p]),
+    "fr_triplet_loss_backward": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int64, ctypes.c_float,
+                                         ctypes.c_float, c_void_p, c_void_p, c_size_t, c_void_p]),
     "fr_op_preprocess": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_int, c_void_p]),
     "fr_op_maxpool": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p,
                               c_int, c_int, c_int, c_int, c_int, c_void_p]),

@@ -445,4 +445,18 @@ size_t arcmargin_workspace(int B, int C, int D);
 hipError_t launch_arcmargin_forward(ArcArgs a, void* ws, hipStream_t s);
 hipError_t launch_arcmargin_backward(ArcArgs a, float* dE, float* dW, void* ws, hipStream_t s);
 
+// Triplet mining and loss (triplet.hip; DESIGN.md §4 "Triplet mining and loss").  Arguments are checked by
+// triplet_api.cpp; every launcher only enqueues on s.  The band height of the mining is what ws_bytes holds.
+size_t triplet_min_workspace(int N);
+size_t triplet_workspace(int N);
+hipError_t launch_triplet_count(const int32_t* labels, int N, int mode, int64_t* lims, hipStream_t s);
+hipError_t launch_triplet_mine(const float* E, int N, int D, const int32_t* labels, int mode, float margin,
+                               const int64_t* lims, int32_t* a_idx, int32_t* p_idx, int32_t* n_idx, int64_t capacity,
+                               uint8_t* semi, void* ws, size_t ws_bytes, hipStream_t s);
+hipError_t launch_triplet_loss_forward(const float* E, int D, const int32_t* a, const int32_t* p, const int32_t* n,
+                                       int64_t T, float margin, float* terms, float* stats, hipStream_t s);
+hipError_t launch_triplet_loss_backward(const float* E, int N, int D, const int32_t* a, const int32_t* p,
+                                        const int32_t* n, int64_t T, float margin, float u, float* dE, void* ws,
+                                        hipStream_t s);
+
 }  // namespace fr

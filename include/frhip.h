@@ -391,6 +391,66 @@ int fr_arcmargin_backward(const float* E, int B, int D, const float* W, int C, c
                           const float* u /*NULL*/, const float* dlogits /*NULL*/, float* dE /*NULL*/,
                           float* dW /*NULL*/, void* ws, size_t ws_bytes, void* stream);
 
+/* ---- Triplet mining and loss (models/facenet: mine_semi_hard_triplets, mine_batch_hard_triplets, mine_triplets,
+ *      TripletLoss = nn.TripletMarginLoss(margin, p=2), and train_facenet.py's compute_triplet_metrics).  Handle-free,
+ *      caller-owned device buffers; E (device f32) [N][D], 16-byte aligned, not necessarily normalised; labels
+ *      (device i32) [N], any values, none is "ignored".
+ *      Mining distance (the Gram form torch.cdist itself uses above 25 rows): g_ij = e_i . e_j (exact f32),
+ *        s_i = sum_k e_ik^2,  d2_ij = max(s_i + s_j - 2 g_ij, 0),  d_ij = sqrt(d2_ij) (IEEE square root).
+ *      The order of every floating-point operation is fixed by (N, D): neither the workspace size nor the banding
+ *      changes a bit.
+ *      Positives of anchor a: rows p != a with labels[p] == labels[a], ascending p.  Negatives: rows of another label.
+ *      An anchor without a positive or without a negative yields nothing (the reference's mine_triplets raises on an
+ *      anchor without negatives; here it is skipped).
+ *        FR_TRIPLET_SEMI_HARD  one triplet per (anchor, positive): among the negatives with d_an > d_ap and
+ *                              d_an < d_ap + margin (f32 sum, f32 comparisons) the one of smallest d_an; if there is
+ *                              none, the negative of smallest d_an of all.
+ *        FR_TRIPLET_BATCH_HARD one triplet per anchor: the positive of largest d_ap, the negative of smallest d_an.
+ *        FR_TRIPLET_FIRST      one triplet per (anchor, positive): the semi-hard negative of lowest index; if there is
+ *                              none, the negative of LARGEST d_an (what the reference's mine_triplets does).
+ *      Every tie goes to the lowest index.  Triplets are listed by ascending anchor, then ascending positive, the same
+ *      in every run (no atomics, no sort).  Every index written lies in [0, N) whatever E holds; which row is chosen
+ *      among non-finite distances is unspecified.  The selection costs T N comparisons (T = number of triplets): one
+ *      class of c rows gives c (c - 1) triplets, so do not feed it one giant class.
+ *      Loss, from the difference form: delta(x, y) = |x - y + 1e-6|_2, h_t = max(margin + delta(a_t, p_t) -
+ *      delta(a_t, n_t), 0), loss = (1 / T) sum_t h_t.  The triplet indices a, p, n (device i32 [T]) must lie in [0, N):
+ *      like labels they are the caller's responsibility and are not checked.
+ *      Limits, each FR_ERR_ARG with a message before any HIP call: 2 <= N <= 32768, D >= 4 and D % 4 == 0, margin
+ *      finite and > 0, mode one of the three, 1 <= T <= 2^40, u finite, required pointers non-null, capacity >= 0,
+ *      ws_bytes at least the stated minimum.  Every result is bitwise repeatable: sums run in a fixed order, no
+ *      floating-point atomics. ---- */
+#define FR_TRIPLET_SEMI_HARD 0
+#define FR_TRIPLET_BATCH_HARD 1
+#define FR_TRIPLET_FIRST 2
+
+/* Recommended bytes of device workspace for fr_triplet_mine (0 and a message on bad arguments): the whole N x N
+ * distance matrix where that is at most 256 MiB, else as many 64-anchor bands as fit, plus the norms.  The minimum
+ * fr_triplet_mine accepts is one band: 4 (64 N + 64 ceil(N / 64)) bytes. */
+size_t fr_triplet_workspace(int N, int D);
+/* lims (device i64) [N + 1]: lims[a] = the number of triplets of anchors < a, lims[N] = T.  From the labels alone. */
+int fr_triplet_count(const int32_t* labels, int N, int mode, int64_t* lims /*[N+1]*/, void* stream);
+/* The triplets of fr_triplet_count's lims (same labels and mode): a_idx, p_idx, n_idx (device i32), triplet
+ * lims[a] + k = anchor a with its k-th positive; positions >= capacity are not written.  semi (device u8, NULL ok):
+ * 1 where the semi-hard branch was taken, 0 where the fallback (always 0 for FR_TRIPLET_BATCH_HARD, which ignores
+ * margin).  Anchors are processed in bands of as many whole multiples of 64 rows as ws_bytes holds. */
+int fr_triplet_mine(const float* E, int N, int D, const int32_t* labels, int mode, float margin, const int64_t* lims,
+                    int32_t* a_idx, int32_t* p_idx, int32_t* n_idx, int64_t capacity, uint8_t* semi /*NULL*/, void* ws,
+                    size_t ws_bytes, void* stream);
+/* terms (device f32, 16-byte aligned) [T][4] = {h_t, |a - p|, |a - n|, margin + delta_ap - delta_an}; stats (device
+ * f32, 16-byte aligned) [4] = {loss, accuracy, pos_dist, neg_dist}: the mean of h_t, the share of triplets with
+ * |a - p| < |a - n|, the means of |a - p| and |a - n| (compute_triplet_metrics: these distances are WITHOUT the
+ * 1e-6).  The per-triplet terms are also the storage the fixed-order reduction reads, so terms is required. */
+int fr_triplet_loss_forward(const float* E, int N, int D, const int32_t* a, const int32_t* p, const int32_t* n,
+                            int64_t T, float margin, float* terms /*[T][4]*/, float* stats /*[4]*/, void* stream);
+/* dE [N][D] (fully written, zeros included) = the gradient of u loss.  A triplet is active when margin + delta_ap -
+ * delta_an >= 0 (clamp_min passes the gradient at equality).  With w_ap = (u / T) / delta_ap and w_an likewise (0
+ * where delta is 0: torch's norm subgradient), an active triplet adds w_ap (a - p + 1e-6) - w_an (a - n + 1e-6) to row
+ * a, -w_ap (a - p + 1e-6) to row p and +w_an (a - n + 1e-6) to row n.  A row's contributions are summed in ascending
+ * triplet index and, within a triplet, in the order anchor, positive, negative.  Each row has one owner, which scans
+ * the three index arrays (N T integer reads).  ws: at least 8 T bytes (the two weights per triplet). */
+int fr_triplet_loss_backward(const float* E, int N, int D, const int32_t* a, const int32_t* p, const int32_t* n,
+                             int64_t T, float margin, float u, float* dE, void* ws, size_t ws_bytes, void* stream);
+
 /* ---- op-level entry points (kernel parity tests and custom graphs) ---- */
 
 /* Implicit-GEMM convolution on NHWC bf16 with fused epilogue:
