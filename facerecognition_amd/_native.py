@@ -174,6 +174,10 @@ _SIGS = {
                                         c_void_p, c_void_p, c_void_p]),
     "fr_triplet_loss_backward": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int64, ctypes.c_float,
                                          ctypes.c_float, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "fr_verify_workspace": (c_size_t, [c_int, c_int]),
+    "fr_verify_pairs": (c_int, [c_void_p, c_int, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p,
+                                c_int, ctypes.c_float, ctypes.c_float, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t,
+                                c_void_p]),
     "fr_op_preprocess": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_int, c_void_p]),
     "fr_op_maxpool": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p,
                               c_int, c_int, c_int, c_int, c_int, c_void_p]),

@@ -459,4 +459,13 @@ hipError_t launch_triplet_loss_backward(const float* E, int N, int D, const int3
                                         const int32_t* n, int64_t T, float margin, float u, float* dE, void* ws,
                                         hipStream_t s);
 
+// All-pairs verification (verify.hip; DESIGN.md §4 "Verification").  Arguments are checked by verify_api.cpp; the
+// launcher only enqueues on s.  thresholds is a host array; the band of rows per launch is what ws_bytes holds.
+size_t verify_min_workspace(int N);
+size_t verify_workspace(int N);
+hipError_t launch_verify_pairs(const float* E, int N, int D, const int32_t* labels, int normalize, const float* thresholds,
+                               int T, uint64_t* counts, uint64_t* totals, uint64_t* hist, int nbins, float lo, float inv_w,
+                               float* row_score, int32_t* row_idx, float* row_sum, void* ws, size_t ws_bytes,
+                               hipStream_t s);
+
 }  // namespace fr

@@ -451,6 +451,48 @@ int fr_triplet_loss_forward(const float* E, int N, int D, const int32_t* a, cons
 int fr_triplet_loss_backward(const float* E, int N, int D, const int32_t* a, const int32_t* p, const int32_t* n,
                              int64_t T, float margin, float u, float* dE, void* ws, size_t ws_bytes, void* stream);
 
+/* ---- All-pairs verification (the 1:1 question behind the reference's compute_verification_accuracy,
+ *      models/arcface/train_arcface.py and models/facenet/train_facenet.py, on EVERY pair of one labelled set instead
+ *      of 10 000 sampled ones).  Handle-free, caller-owned device buffers; E (device f32) [N][D], 16-byte aligned;
+ *      labels (device i32) [N], any values, none is "ignored".  No N x N matrix is stored.
+ *      Score of the pair (i, j): g_ij = e_i . e_j (exact f32, fr_match_topk's operation order).  normalize = 1:
+ *        r_i = 1 / (sqrt(sum_k e_ik^2) + 1e-8f),  s_ij = (g_ij r_i) r_j
+ *      (the reference's a / (|a| + 1e-8) applied to the score; every operation rounded to f32, IEEE square root and
+ *      division).  normalize = 0: s_ij = g_ij, the rows as given.
+ *      A pair is genuine when labels[i] == labels[j], otherwise an impostor; the diagonal is never a pair.
+ *      The order of every floating-point operation is fixed by (N, D): the workspace size and the banding change no
+ *      bit, and every result is bitwise repeatable (integer atomics only).
+ *      With non-finite scores which row is chosen is unspecified; every index written lies in [-1, N).
+ *      Limits, each FR_ERR_ARG with a message before any HIP call: 2 <= N <= 2^22, D >= 4 and D % 4 == 0, normalize
+ *      0 or 1, 0 <= T <= 64 with thresholds and counts non-null when T > 0, every threshold finite, 1 <= nbins <= 2048
+ *      and finite hi > lo when hist is given, E, labels, totals and ws non-null, row_score and row_idx together or not
+ *      at all, ws_bytes at least the stated minimum. ---- */
+#define FR_VERIFY_MAX_THRESHOLDS 64
+
+/* Recommended bytes of device workspace for fr_verify_pairs (0 and a message on bad arguments): the norms and every
+ * row's partial results (32 bytes per row and 1024-column chunk) where those are at most 256 MiB, else as many 64-row
+ * bands as fit.  The minimum fr_verify_pairs accepts is one band: 4 * 64 ceil(N / 64) + 2048 ceil(N / 1024) bytes. */
+size_t fr_verify_workspace(int N, int D);
+/* One pass over all pairs.  thresholds: HOST f32 [T] (read before the call returns).  Outputs, all on the device:
+ *   totals [2] u64 (required)   the number of genuine and of impostor pairs i < j; overwritten.
+ *   counts [T][2] u64           per threshold the number of genuine and of impostor pairs i < j with s > t (strict f32
+ *                               comparison, the reference's rule, not the engine's >=); overwritten.
+ *   hist [2][nbins] u64 (NULL)  the genuine and the impostor histogram over i < j, ADDED to the caller's counts; bin =
+ *                               clamp((int)floorf((s - lo) * inv_w), 0, nbins - 1) with inv_w = (float)nbins / (hi - lo)
+ *                               rounded once (fr_match_eval's rule).
+ *   row_score [N][3] f32, row_idx [N][3] i32 (both or NULL)   per row i over all j != i: its best genuine mate (largest
+ *                               s), its worst genuine mate (smallest s) and its best impostor (largest s); ties to the
+ *                               lowest j; where there is no such j the score is -inf, +inf, -inf and the index -1.
+ *   row_sum [N][2] f32 (NULL)   per row the sum of its genuine and of its impostor scores over j != i: per 1024-column
+ *                               chunk a lane's columns (j mod 16 equal) in ascending j, a 16-lane tree, then the chunks in
+ *                               ascending order.
+ * Without row outputs only the upper triangle is computed.  Stream-ordered, no host synchronisation inside. */
+int fr_verify_pairs(const float* E, int N, int D, const int32_t* labels, int normalize,
+                    const float* thresholds /*host [T]*/, int T, uint64_t* counts /*[T][2]*/,
+                    uint64_t* totals /*[2]*/, uint64_t* hist /*[2][nbins], NULL*/, int nbins, float lo, float hi,
+                    float* row_score /*[N][3], NULL*/, int32_t* row_idx /*[N][3], NULL*/,
+                    float* row_sum /*[N][2], NULL*/, void* ws, size_t ws_bytes, void* stream);
+
 /* ---- op-level entry points (kernel parity tests and custom graphs) ---- */
 
 /* Implicit-GEMM convolution on NHWC bf16 with fused epilogue:
