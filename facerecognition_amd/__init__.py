@@ -38,9 +38,13 @@ def __getattr__(name):  # lazy: importing the package must not initialise the GP
     if name in _VERIFICATION:
         from . import verification
         return getattr(verification, name)
+    if name in _HEAD:
+        from . import head
+        return getattr(head, name)
     raise AttributeError(name)
 
 
+_HEAD = ("EmbeddingHead",)
 _VERIFICATION = ("verify_pairs", "compute_verification_accuracy", "verification_report")
 _TRIPLET = ("TripletLoss", "mine_triplets", "mine_semi_hard_triplets", "mine_batch_hard_triplets", "triplet_loss",
             "online_triplet_loss", "compute_triplet_metrics")

@@ -2071,6 +2071,46 @@ int fr_explain(fr_handle* h, const void* in, int in_fmt, int B, int H, int W, co
     return FR_OK;
 }
 
+int fr_features_dim(const fr_handle* h) {
+    if (!h) { set_error("fr_features_dim: null handle"); return FR_ERR_ARG; }
+    if (!h->loaded || h->ops.empty() || h->ops.back().kind != OP_HEAD) {
+        set_error("fr_features_dim: weights not loaded");
+        return FR_ERR_STATE;
+    }
+    return h->convw[h->ops.back().wi].K;
+}
+
+int fr_features(fr_handle* h, const void* in, int in_fmt, int B, int H, int W, float* out, void* stream) {
+    if (!h) { set_error("fr_features: null handle"); return FR_ERR_ARG; }
+    std::lock_guard<std::mutex> lk(h->mu);
+    if (!h->loaded || h->ops.empty() || h->ops.back().kind != OP_HEAD) {
+        set_error("fr_features: weights not loaded");
+        return FR_ERR_STATE;
+    }
+    if (!in || !out || B <= 0) { set_error("fr_features: bad argument"); return FR_ERR_ARG; }
+    if (h->max_batch <= 0) { set_error("fr_features: nothing reserved (call fr_reserve first)"); return FR_ERR_STATE; }
+    if (B > h->max_batch) {
+        set_error("fr_features: B = " + std::to_string(B) + " is above the reserved batch " + std::to_string(h->max_batch) +
+                  " (fr_reserve)");
+        return FR_ERR_ARG;
+    }
+    if (B > embed_chunk(h)) {  // a chunked forward leaves only its last chunk's activations behind
+        set_error("fr_features: B is above the largest single forward (" + std::to_string(embed_chunk(h)) + ")");
+        return FR_ERR_ARG;
+    }
+    const Op& head = h->ops.back();
+    const auto& t = h->tensors[head.in];
+    const int K = h->convw[head.wi].K, P = t.H * t.W;
+    if (P * t.C != K || t.C % 8) { set_error("fr_features: head input does not match the head's K"); return FR_ERR_ARG; }
+    // the forward is waited for (no FR_EMBED_ASYNC), so the head's input below is that of valid embeddings; the
+    // embeddings themselves go to fr_explain's scratch
+    if (!h->ex_emb) { set_error("fr_features: nothing reserved (call fr_reserve first)"); return FR_ERR_STATE; }
+    const int rc = embed_locked(h, in, in_fmt, B, H, W, h->ex_emb, FR_EMBED_RAW, stream);
+    if (rc) return rc;
+    FR_HIP_CHECK(launch_features_cvt(t.dev, B, P, t.C, h->dtype == FR_DTYPE_F16 || t.f16, out, (hipStream_t)stream));
+    return FR_OK;
+}
+
 int fr_gallery_set(fr_handle* h, const float* G, int64_t N, int D, int64_t index_base, int g_on_device) {
     if (!h || (!G && N > 0) || N < 0 || D <= 0 || D % 4 != 0 || N + index_base > INT32_MAX) {
         set_error("fr_gallery_set: bad argument (D must be a multiple of 4, indices must fit int32)");

@@ -468,4 +468,30 @@ hipError_t launch_verify_pairs(const float* E, int N, int D, const int32_t* labe
                                float* row_score, int32_t* row_idx, float* row_sum, void* ws, size_t ws_bytes,
                                hipStream_t s);
 
+// fr_features (misc.hip): out [B][C P] f32 with out[b][c P + p] = x[b][p][c] (16-bit NHWC; P = 1: a plain convert).
+hipError_t launch_features_cvt(const bf16_t* x, int B, int P, int C, int f16, float* out, hipStream_t s);
+
+// Head training (head_train.hip; DESIGN.md §4 "Head training").  Arguments are checked by head_api.cpp; every
+// launcher only enqueues on s.
+struct HeadArgs {
+    const float* X;  // [B][K]
+    const float* W;  // [N][K]
+    int B, K, S, N;
+    const float *gamma1, *beta1;  // [K / S] or null (no input BN)
+    const float *mean1, *rstd1;   // [K / S]: what the input BN normalises with (the forward's outputs)
+    bool batch_stats;
+    uint32_t thresh;  // keep iff the Philox word >= thresh; 0 with keep_scale 1: no dropout, no generator
+    float keep_scale;
+    bool dropout;
+    uint64_t seed, offset;
+};
+size_t head_workspace(int B, int K, int N);
+hipError_t launch_head_train_forward(HeadArgs a, const float* bias, float* rm1, float* rv1, const float* gamma2,
+                                     const float* beta2, float* rm2, float* rv2, float eps, float momentum, float* Y,
+                                     float* Z, float* mean1, float* rstd1, float* mean2, float* rstd2, float* A, void* ws,
+                                     hipStream_t s);
+hipError_t launch_head_train_backward(HeadArgs a, const float* gamma2, const float* mean2, const float* rstd2,
+                                      const float* Z, const float* dY, float* dX, float* dW, float* dbias, float* dgamma1,
+                                      float* dbeta1, float* dgamma2, float* dbeta2, void* ws, hipStream_t s);
+
 }  // namespace fr

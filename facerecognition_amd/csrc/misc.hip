@@ -379,6 +379,35 @@ hipError_t launch_avgpool(const bf16_t* x, int B, int H, int W, int C, bf16_t* y
     return hipGetLastError();
 }
 
+// out[b][c P + p] = x[b][p][c]: thread = (b, p, 8 channels)
+template <bool F16>
+__global__ __launch_bounds__(256) void features_cvt_kernel(const bf16_t* __restrict__ x, int64_t total, int P, int C,
+                                                           float* __restrict__ out) {
+    const int64_t it = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (it >= total) return;
+    const int G = C / 8;
+    const int g = (int)(it % G);
+    const int64_t bp = it / G;
+    const int p = (int)(bp % P);
+    const int64_t b = bp / P;
+    float f[8];
+    Num<F16>::unpack8(*(const uint4*)(x + (size_t)bp * C + g * 8), f);
+    float* o = out + (size_t)b * C * P + (size_t)(g * 8) * P + p;
+#pragma unroll
+    for (int e = 0; e < 8; ++e) o[(size_t)e * P] = f[e];
+}
+
+hipError_t launch_features_cvt(const bf16_t* x, int B, int P, int C, int f16, float* out, hipStream_t s) {
+    if (B < 1 || P < 1 || C < 8 || C % 8) return hipErrorInvalidValue;
+    const int64_t total = (int64_t)B * P * (C / 8);
+    const dim3 grid((unsigned)((total + 255) / 256));
+    if (f16)
+        hipLaunchKernelGGL(features_cvt_kernel<true>, grid, dim3(256), 0, s, x, total, P, C, out);
+    else
+        hipLaunchKernelGGL(features_cvt_kernel<false>, grid, dim3(256), 0, s, x, total, P, C, out);
+    return hipGetLastError();
+}
+
 hipError_t launch_head_finalize(const float* partial, int split, int B, int N, int Npad, const float* bias,
                                 int normalize, float* out, hipStream_t s) {
     if (N % 4 || N > 1024 || Npad % 4) return hipErrorInvalidValue;

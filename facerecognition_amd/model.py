@@ -116,6 +116,26 @@ class FRModel:
                 "fr_embed")
         return out
 
+    @property
+    def feature_dim(self) -> int:
+        """K of the tensor the embedding head reads (fr_features_dim)."""
+        k = int(N.lib().fr_features_dim(self._h))
+        N.check(k if k < 0 else 0, "fr_features_dim")
+        return k
+
+    def features(self, x):
+        """Device f32 [B, K] input of the embedding head in torch's flatten order (fr_features): one forward, then
+        the 16-bit activations the engine's own head reads, converted.  Feeds facerecognition_amd.head.EmbeddingHead."""
+        import torch
+
+        x, fmt, H, W = self._prep(x)
+        B = int(x.shape[0])
+        self.reserve(B)  # fr_features takes no batch above the reserved one (a no-op once reserved)
+        out = torch.empty((B, self.feature_dim), dtype=torch.float32, device=self.device)
+        N.check(N.lib().fr_features(self._h, N.ptr(x), fmt, B, H, W, N.ptr(out), N.stream_ptr(self.device)),
+                "fr_features")
+        return out
+
     def explain_shape(self):
         """(h, w, C) of the explained layer (fr_explain_shape)."""
         h, w, c = ctypes.c_int(), ctypes.c_int(), ctypes.c_int()

@@ -121,6 +121,15 @@ int fr_explain_shape(const fr_handle* h, int* th, int* tw, int* tc);
 int fr_explain(fr_handle* h, const void* in, int in_fmt, int B, int H, int W, const float* target,
                float* cam, float* low, float* emb, void* stream);
 
+/* K of the tensor the embedding head reads: 2048 (resnet50_arcface), 25088 (iresnet100), 1792 (irv1_facenet);
+ * FR_ERR_ARG on a null handle, FR_ERR_STATE before the weights are loaded. */
+int fr_features_dim(const fr_handle* h);
+/* One forward under fr_explain's rules (waited for, B at most the reserved batch and at most one chunk, else
+ * FR_ERR_ARG), then the head's input as device f32 out [B][K] in torch's flatten order: the pooled vector of the two
+ * pooled models, c * 49 + p (NCHW) for IResNet100 (whose device tensor is NHWC).  The values are the 16-bit
+ * activations the engine's own head reads, converted to f32.  This is the input of fr_head_forward. */
+int fr_features(fr_handle* h, const void* in, int in_fmt, int B, int H, int W, float* out, void* stream);
+
 /* Synchronize `stream`, then report (once) a split-stage wait that ran out in an FR_EMBED_ASYNC forward
  * of this handle since the last report: FR_ERR_STAGE, else FR_OK. */
 int fr_sync_check(fr_handle* h, void* stream);
@@ -492,6 +501,61 @@ int fr_verify_pairs(const float* E, int N, int D, const int32_t* labels, int nor
                     uint64_t* totals /*[2]*/, uint64_t* hist /*[2][nbins], NULL*/, int nbins, float lo, float hi,
                     float* row_score /*[N][3], NULL*/, int32_t* row_idx /*[N][3], NULL*/,
                     float* row_sum /*[N][2], NULL*/, void* ws, size_t ws_bytes, void* stream);
+
+/* ---- Head training: the embedding head between a frozen trunk and the losses above, forward and backward
+ *      (ArcFaceModel's bn1 -> dropout -> fc -> bn2, IResNet100's bn2 -> flatten -> fc -> features, FaceNet's
+ *      dropout -> last_linear -> last_bn).  Handle-free, caller-owned f32 device buffers; X, W, Y, dW, dX (and A, Z, dY)
+ *      16-byte aligned.
+ *      X [B][K] with K = Cin S; feature f belongs to input-BN channel f / S (S = 1: BatchNorm1d; S = 49: IResNet100's
+ *      BatchNorm2d before the flatten).  W [N][K], bias [N] or NULL, gamma1 / beta1 [Cin] or both NULL (no input BN),
+ *      gamma2 / beta2 [N].  flags: FR_HEAD_BATCH_STATS (both BNs use batch statistics and update the running ones; else
+ *      they use the running ones and update nothing) | FR_HEAD_DROPOUT (dropout is active).  freeze_bn is DROPOUT alone.
+ *      Forward, n1 = B S, n2 = B:
+ *        mean1_c = sum x / n1, var1_c = sum (x - mean1_c)^2 / n1 (two passes, biased), rstd1 = 1 / sqrt(var1 + eps) (IEEE),
+ *        running_mean1 <- (1 - mom) running_mean1 + mom mean1, running_var1 <- (1 - mom) running_var1 + mom var1 n1 / (n1 - 1)
+ *        (running statistics: mean1 = running_mean1, var1 = running_var1);  H = gamma1 (x - mean1) rstd1 + beta1  (no BN: H = X)
+ *        A = H m / (1 - p): Philox4x32-10 (Random123 constants) with key (lo32 seed, hi32 seed) and counter
+ *        (lo32 (i >> 2), hi32 (i >> 2), lo32 offset, hi32 offset) for the 64-bit element index i = b K + f; r = output word
+ *        i & 3; keep iff r >= T = (uint32) floor(p 2^32) (in double); kept: H (1.0f / (1.0f - p)), dropped: +0.0f;
+ *        p = 0 or the flag off: A = H
+ *        Z = A W^T + bias (exact f32; split-K partials merged in split order, the split a function of (B, K, N) alone)
+ *        mean2, var2, rstd2 and the running update over the B rows of Z likewise;  Y = gamma2 (Z - mean2) rstd2 + beta2
+ *      Backward from dY [B][N], z^ = (Z - mean2) rstd2, x^ = (x - mean1) rstd1:
+ *        batch statistics: dgamma2 = sum_b dY z^, dbeta2 = sum_b dY, dZ = gamma2 rstd2 (dY - dbeta2 / n2 - z^ dgamma2 / n2)
+ *        running statistics: the same dgamma2, dbeta2; dZ = dY gamma2 rstd2
+ *        dW = dZ^T A (every row has one owner), dbias = sum_b dZ, dA = dZ W, dH = dA m / (1 - p)
+ *        dgamma1 = sum dH x^, dbeta1 = sum dH (over B S), dX = gamma1 rstd1 (dH - dbeta1 / n1 - x^ dgamma1 / n1)
+ *        (running statistics: dX = dH gamma1 rstd1; no input BN: dX = dH).  The mask is regenerated from (seed, offset).
+ *      Limits, each FR_ERR_ARG with a message before any HIP call: B >= 1; with BATCH_STATS B S >= 2 where the input BN
+ *      is present and B >= 2; K, N >= 4 and multiples of 4; S >= 1 and K % S == 0; B K, N K, B N <= 2^40 (all indexing is
+ *      64-bit) and, for the launch grids, B <= 2^24 and K, N <= 4194240; p in [0, 1); eps finite and > 0; momentum in [0, 1]; no unknown flag bits; gamma1 and beta1 both given
+ *      or both NULL; running statistics present whenever a BN is; required pointers non-null; ws_bytes >=
+ *      fr_head_workspace.  Every result is bitwise repeatable and independent of the workspace size: sums run in an
+ *      order fixed by (B, K, S, N), no floating-point atomics. ---- */
+#define FR_HEAD_BATCH_STATS 1
+#define FR_HEAD_DROPOUT 2
+
+/* Bytes of device workspace the two calls below need (0 and a message on bad arguments): the split-K partials of Z,
+ * and for the backward dZ [B][N] plus per-64-row column sums for the input BN -- never a B x K gradient. */
+size_t fr_head_workspace(int B, int K, int N);
+/* Y [B][N], Z [B][N] (the Linear's output, saved for the backward), mean1 / rstd1 [Cin] (NULL without the input BN),
+ * mean2 / rstd2 [N], and A [B][K] when non-NULL (the Linear's input).  running_* are read, and with BATCH_STATS
+ * written. */
+int fr_head_forward(const float* X, int B, int K, int S, const float* W, int N, const float* bias /*NULL*/,
+                    const float* gamma1 /*NULL*/, const float* beta1 /*NULL*/, float* running_mean1 /*NULL*/,
+                    float* running_var1 /*NULL*/, const float* gamma2, const float* beta2, float* running_mean2,
+                    float* running_var2, int flags, float p, float eps, float momentum, uint64_t seed, uint64_t offset,
+                    float* Y, float* Z, float* mean1 /*NULL*/, float* rstd1 /*NULL*/, float* mean2, float* rstd2,
+                    float* A /*NULL*/, void* ws, size_t ws_bytes, void* stream);
+/* Any of dX [B][K], dW [N][K], dbias [N], dgamma1 / dbeta1 [Cin], dgamma2 / dbeta2 [N] (at least one non-NULL; dgamma1
+ * and dbeta1 only with the input BN).  flags, p, seed, offset, Z and the four statistics are the forward's.  With dX
+ * NULL (a frozen trunk) no B x K gradient is written anywhere. */
+int fr_head_backward(const float* X, int B, int K, int S, const float* W, int N, const float* gamma1 /*NULL*/,
+                     const float* beta1 /*NULL*/, const float* gamma2, int flags, float p, uint64_t seed,
+                     uint64_t offset, const float* mean1 /*NULL*/, const float* rstd1 /*NULL*/, const float* mean2,
+                     const float* rstd2, const float* Z, const float* dY, float* dX /*NULL*/, float* dW /*NULL*/,
+                     float* dbias /*NULL*/, float* dgamma1 /*NULL*/, float* dbeta1 /*NULL*/, float* dgamma2 /*NULL*/,
+                     float* dbeta2 /*NULL*/, void* ws, size_t ws_bytes, void* stream);
 
 /* ---- op-level entry points (kernel parity tests and custom graphs) ---- */
 
