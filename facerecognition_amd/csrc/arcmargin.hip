@@ -4,7 +4,7 @@
 // Replaces: models/arcface/arcface_model.py:23-62 (cosine, one-hot and output, three B x C tensors, plus
 // autograd's copies) and the criterion of train_arcface.py:109-111.
 //
-// Scores are exact f32: match.hip's v_mfma_f32_16x16x4f32 tile loop (64 rows x 64 rows, D staged through LDS in
+// Scores are exact f32: score_tile.h's v_mfma_f32_16x16x4f32 tile loop (64 rows x 64 rows, D staged through LDS in
 // 64-float chunks, k = 16 t16 + 4 (lane >> 4) + c), the raw dot scaled by inv_e[b] inv_w[j] in the epilogue.
 //   norms_kernel    inv[r] = 1 / max(|x_r|, 1e-12), IEEE sqrt and division (rows of norm 1 give exactly 1)
 //   fwd_kernel      64 probes x one class split: per 64-class tile the label transform and an online
@@ -17,35 +17,22 @@
 //   jacobian_kernel partials in split order, then the normalise Jacobian (d - (d . x^) x^) / max(|x|, 1e-12)
 //   The next D chunk is loaded into registers while the current chunk's MFMAs run (score and product loops).
 // No float atomics; every sum runs in an order fixed by (B, C, D).
-#include "kernels.h"
+#include "score_tile.h"
 #include <float.h>
 
 #include <algorithm>
 
 namespace fr {
+using namespace tile;
 namespace {
 
-constexpr int MT = 64;  // rows per tile, both sides
-constexpr int KC = 64;  // D chunk (floats)
-constexpr int LD = KC + 4;
-constexpr int SLD = MT + 1;
 constexpr int PREC = 8;  // floats per forward partial: {max, sum exp, sum z, z at y, z at y', -, -, -}
 
 __global__ __launch_bounds__(256) void norms_kernel(const float* __restrict__ X, int64_t R, int D, float* __restrict__ inv) {
     const int lane = threadIdx.x & 63;
     const int64_t r = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
     if (r >= R) return;
-    const float* x = X + (size_t)r * D;
-    float ss = 0.f;
-    for (int d = 4 * lane; d < D; d += 256) {
-        const float4 v = *(const float4*)(x + d);
-        ss += v.x * v.x;
-        ss += v.y * v.y;
-        ss += v.z * v.z;
-        ss += v.w * v.w;
-    }
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) ss += __shfl_xor(ss, o);
+    const float ss = row_sqsum(X + (size_t)r * D, D);
     if (lane == 0) inv[r] = __fdiv_rn(1.f, fmaxf(__fsqrt_rn(ss), 1e-12f));
 }
 
@@ -56,61 +43,6 @@ __device__ __forceinline__ float margin_z(const ArcArgs& a, float c, float* dz) 
     const bool on = a.easy_margin ? (c > 0.f) : (c > a.th);
     *dz = on ? a.cos_m + (q >= 1e-7f ? a.sin_m * c / sine : 0.f) : 1.f;
     return on ? c * a.cos_m - sine * a.sin_m : (a.easy_margin ? c : c - a.mm);
-}
-
-// acc[j][r] = sum_d X[x0 + 16 wave + 4 (lane >> 4) + r][d] Y[t0 + 16 j + (lane & 15)][d]; rows past rx / ry and
-// columns past D read as zero.  Ends with a barrier: sX / sY are free again.
-__device__ __forceinline__ void score_tile(const float* __restrict__ X, int64_t rx, int64_t x0, const float* __restrict__ Y,
-                                           int64_t ry, int64_t t0, int D, float* sX, float* sY, f32x4_t (&acc)[4]) {
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-#pragma unroll
-    for (int j = 0; j < 4; ++j) acc[j] = (f32x4_t){0.f, 0.f, 0.f, 0.f};
-    // chunk d0 + KC is loaded into registers while chunk d0's MFMAs run
-    float4 xv[4], yv[4];
-    auto load = [&](int d0) {
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            const int q = tid + 256 * i;
-            const int row = q >> 4, c4 = (q & 15) * 4;
-            xv[i] = yv[i] = make_float4(0.f, 0.f, 0.f, 0.f);
-            if (x0 + row < rx && d0 + c4 < D) xv[i] = *(const float4*)(X + (size_t)(x0 + row) * D + d0 + c4);
-            if (t0 + row < ry && d0 + c4 < D) yv[i] = *(const float4*)(Y + (size_t)(t0 + row) * D + d0 + c4);
-        }
-    };
-    load(0);
-    for (int d0 = 0; d0 < D; d0 += KC) {
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            const int q = tid + 256 * i;
-            const int row = q >> 4, c4 = (q & 15) * 4;
-            *(float4*)(sX + row * LD + c4) = xv[i];
-            *(float4*)(sY + row * LD + c4) = yv[i];
-        }
-        __syncthreads();
-        if (d0 + KC < D) load(d0 + KC);
-#pragma unroll
-        for (int t16 = 0; t16 < KC / 16; ++t16) {
-            const int kof = 16 * t16 + 4 * (lane >> 4);
-            const float4 a4 = *(const float4*)(sX + (16 * wave + (lane & 15)) * LD + kof);
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                const float4 b4 = *(const float4*)(sY + (16 * j + (lane & 15)) * LD + kof);
-                acc[j] = __builtin_amdgcn_mfma_f32_16x16x4f32(a4.x, b4.x, acc[j], 0, 0, 0);
-                acc[j] = __builtin_amdgcn_mfma_f32_16x16x4f32(a4.y, b4.y, acc[j], 0, 0, 0);
-                acc[j] = __builtin_amdgcn_mfma_f32_16x16x4f32(a4.z, b4.z, acc[j], 0, 0, 0);
-                acc[j] = __builtin_amdgcn_mfma_f32_16x16x4f32(a4.w, b4.w, acc[j], 0, 0, 0);
-            }
-        }
-        __syncthreads();
-    }
-}
-
-__device__ __forceinline__ void store_tile(float* sS, const f32x4_t (&acc)[4]) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-    for (int j = 0; j < 4; ++j)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) sS[(16 * wave + 4 * (lane >> 4) + r) * SLD + 16 * j + (lane & 15)] = acc[j][r];
 }
 
 __global__ __launch_bounds__(256) void fwd_kernel(const ArcArgs a, float* __restrict__ part) {
@@ -132,8 +64,8 @@ __global__ __launch_bounds__(256) void fwd_kernel(const ArcArgs a, float* __rest
 
     for (int64_t t0 = c_begin; t0 < c_end; t0 += MT) {
         f32x4_t acc[4];
-        score_tile(a.E, a.B, p0, a.W, c_end, t0, a.D, sXY, sXY + MT * LD, acc);
-        store_tile(sS, acc);
+        score_tile_prefetch<int64_t, int64_t>(a.E, a.B, p0, a.W, c_end, t0, a.D, sXY, sXY + MT * LD, acc);
+        store_score_tile(sS, acc);
         __syncthreads();
         const float* row = sS + my_p * SLD + my_sub * 16;
         const int64_t jb = t0 + my_sub * 16;
@@ -285,8 +217,8 @@ __global__ __launch_bounds__(256) void bwd_kernel(const ArcArgs a, float* __rest
 
     for (int64_t t0 = y_begin; t0 < y_end; t0 += MT) {
         f32x4_t sc[4];
-        score_tile(X, rx, x0, Y, y_end, t0, D, sX, sY, sc);
-        store_tile(sS, sc);
+        score_tile_prefetch<int64_t, int64_t>(X, rx, x0, Y, y_end, t0, D, sX, sY, sc);
+        store_score_tile(sS, sc);
         __syncthreads();
         {   // the score tile -> g, scaled by the walked side's 1 / norm (its rows enter the product raw)
             float* row = sS + my_r * SLD + my_sub * 16;

@@ -7,13 +7,14 @@
 //   notebook batched np.dot + argmax/argsort evaluate_arcface_kaggle.ipynb cells 15-16
 //
 // Scores are exact f32 (v_mfma_f32_16x16x4_f32: an fmaf chain per lane group, no reduced-
-// precision path).  Each block owns 64 probes x one gallery split; it walks the split in
+// precision path; the tile loops are score_tile.h's, shared with every other exact-score
+// kernel).  Each block owns 64 probes x one gallery split; it walks the split in
 // 64-row tiles (D staged through LDS in 64-float chunks), writes the 64x64 score tile to
 // LDS, and 4 threads per probe keep sorted register top-k lists (strict comparator with
 // index tie-break, so equal scores keep the lower index first exactly like np.argmax and
 // Python's stable sort).  A merge kernel (also used after the multi-GPU all-gather) folds
 // the per-split lists.
-#include "kernels.h"
+#include "score_tile.h"
 #include <float.h>
 #include <limits.h>
 
@@ -21,16 +22,8 @@
 #include <cstdlib>
 
 namespace fr {
+using namespace tile;
 namespace {
-
-constexpr int MP = 64;  // probes per block
-constexpr int MG = 64;  // gallery rows per tile
-constexpr int KC = 64;  // D chunk (floats)
-constexpr int LD = KC + 4;
-
-__device__ __forceinline__ bool better(float s1, int i1, float s2, int i2) {
-    return s1 > s2 || (s1 == s2 && i1 < i2);
-}
 
 // Insert (s, idx) into a list sorted by better(): branch-free.  b[q] = the candidate beats entry q is
 // monotone in q, so entry q becomes entry q-1 (b[q-1]), the candidate (first b), or stays.  (A swap chain
@@ -63,7 +56,7 @@ __global__ __launch_bounds__(256) void match_partial_kernel(const float* __restr
     float* sP = sPG;
     float* sG = sPG + MP * LD;
 
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int tid = threadIdx.x;
     const int p0 = blockIdx.x * MP;
     const int split = blockIdx.y;
     const int64_t g_begin = (int64_t)split * rows_per_split;
@@ -78,42 +71,8 @@ __global__ __launch_bounds__(256) void match_partial_kernel(const float* __restr
 
     for (int64_t t0 = g_begin; t0 < g_end; t0 += MG) {
         f32x4_t acc[4];
-#pragma unroll
-        for (int j = 0; j < 4; ++j) acc[j] = (f32x4_t){0.f, 0.f, 0.f, 0.f};
-        for (int d0 = 0; d0 < D; d0 += KC) {
-            // stage P[p0:p0+64][d0:d0+64] and G[t0:t0+64][d0:d0+64]
-#pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                const int q = tid + 256 * i;
-                const int row = q >> 4, c4 = (q & 15) * 4;
-                float4 pv = make_float4(0.f, 0.f, 0.f, 0.f), gv = pv;
-                if (p0 + row < B && d0 + c4 < D) pv = *(const float4*)(P + (size_t)(p0 + row) * D + d0 + c4);
-                if (t0 + row < g_end && d0 + c4 < D) gv = *(const float4*)(G + (size_t)(t0 + row) * D + d0 + c4);
-                *(float4*)(sP + row * LD + c4) = pv;
-                *(float4*)(sG + row * LD + c4) = gv;
-            }
-            __syncthreads();
-#pragma unroll
-            for (int t16 = 0; t16 < KC / 16; ++t16) {
-                const int kof = 16 * t16 + 4 * (lane >> 4);
-                const float4 a4 = *(const float4*)(sP + (16 * wave + (lane & 15)) * LD + kof);
-#pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    const float4 b4 = *(const float4*)(sG + (16 * j + (lane & 15)) * LD + kof);
-                    acc[j] = __builtin_amdgcn_mfma_f32_16x16x4f32(a4.x, b4.x, acc[j], 0, 0, 0);
-                    acc[j] = __builtin_amdgcn_mfma_f32_16x16x4f32(a4.y, b4.y, acc[j], 0, 0, 0);
-                    acc[j] = __builtin_amdgcn_mfma_f32_16x16x4f32(a4.z, b4.z, acc[j], 0, 0, 0);
-                    acc[j] = __builtin_amdgcn_mfma_f32_16x16x4f32(a4.w, b4.w, acc[j], 0, 0, 0);
-                }
-            }
-            __syncthreads();
-        }
-        // acc[j][r] = score(probe 16*wave + 4*(lane>>4) + r, gallery row t0 + 16*j + (lane&15))
-#pragma unroll
-        for (int j = 0; j < 4; ++j)
-#pragma unroll
-            for (int r = 0; r < 4; ++r)
-                sS[(16 * wave + 4 * (lane >> 4) + r) * (MG + 1) + 16 * j + (lane & 15)] = acc[j][r];
+        score_tile_staged(P, B, p0, G, g_end, t0, D, sP, sG, acc);
+        store_score_tile(sS, acc);
         __syncthreads();
         // filter against this lane's current K-th best first: after the lists fill almost no score
         // qualifies, and the (divergent) sorted insert runs only for the few that do
@@ -162,33 +121,12 @@ __global__ __launch_bounds__(256) void match_partial_kernel(const float* __restr
     }
 }
 
-// D = 512 variant of match_partial_kernel with the same scores bit for bit (the same v_mfma_f32_16x16x4f32
-// sequence per output: k = 16 t16 + 4 (lane >> 4) + c) and the same candidate lists.  Each wave keeps its
-// 16 probes' A fragments in registers for the whole split (32 float4 per lane, loaded once), so only
-// gallery rows move through LDS: 64-row x 64-float chunks (256-B rows, 16-B slots XOR-swizzled with the
-// row: conflict-free fragment reads) LDS-DMA'd three chunks ahead into a 4-buffer ring, counted vmcnt
-// waits and one LDS-only barrier per chunk.  (The old kernel staged both operands per chunk through
-// registers behind full barriers; register prefetch one chunk ahead left each block one 16-KB load in
-// flight and ran 74 us at 256 x 10k, latency bound.)
-constexpr int D512 = 512;
-constexpr int NBUF = 4;                    // chunk ring depth (3 chunks in flight)
-constexpr int CHUNK_B = MG * KC * 4;       // 16384
-constexpr int P512_LDS = NBUF * CHUNK_B + MP * (MG + 1) * 4;
-__device__ __forceinline__ void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
-
-// 16-B LDS-DMA from inline asm (lane l lands at lds_addr + 16 l): the compiler does not see the LDS write,
-// so it adds no vmcnt(0) before later LDS accesses; the kernel's own counted waits cover it
-typedef int v4i32 __attribute__((ext_vector_type(4)));
-#pragma clang diagnostic push
-#pragma clang diagnostic ignored "-Winline-asm"
-__device__ __forceinline__ void dma16_asm(const v4i32& rsrc, uint32_t lds_addr, uint32_t voff) {
-    asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tbuffer_load_dwordx4 %0, %1, 0 offen lds"
-                 :
-                 : "v"(voff), "s"(rsrc), "s"(__builtin_amdgcn_readfirstlane(lds_addr))
-                 : "memory", "m0");
-}
-#pragma clang diagnostic pop
-
+// D = 512 variant of match_partial_kernel with the same scores bit for bit and the same candidate lists: the
+// register-probe, LDS-DMA ring that score_tile.h describes (its constants, lds_barrier and dma16_asm are the
+// header's) with the filtered top-k insert per tile.  This kernel keeps its own copy of the loop that the header's
+// p512_* pieces hold for eval_p512_kernel and range_p512_kernel: put together from the pieces it compiled to 236
+// instead of 256 VGPRs and measured 0.6 % slower at 20387 x 9343 (two tiles per split), outside the 0.3 % that
+// repeated runs of one build spread over.  A change to the ring's waits or swizzle is made in p512_tile and here.
 template <int KMAX>
 __global__ __launch_bounds__(256, 1) void match_p512_kernel(const float* __restrict__ P, int B,
                                                             const float* __restrict__ G, int64_t N, int k,
@@ -455,7 +393,7 @@ hipError_t launch_match_topk(const float* P, int B, const float* G, int64_t N, i
                              float* cand_s, int32_t* cand_i, int n_split, int64_t rows_per_split, hipStream_t s) {
     dim3 grid((B + MP - 1) / MP, n_split);
     if (D == D512 && p512_enabled() && B > 0 && k <= 8) {  // (16-deep lists would spill next to the register probes)
-        if (rows_per_split > 64 * MG) return hipErrorInvalidValue;  // the plan's bound (32-bit DMA offsets)
+        if (rows_per_split > P512_MAX_TILES * MG) return hipErrorInvalidValue;  // the plan's bound (32-bit DMA offsets)
         // lists exactly as deep as needed for the usual k <= 5 (top-5 is the reference's default)
         auto kern = k <= 5 ? match_p512_kernel<5> : match_p512_kernel<8>;
         if (hipError_t e = lds_opt_in((const void*)kern, P512_LDS); e != hipSuccess) return e;
@@ -514,37 +452,8 @@ __global__ __launch_bounds__(256) void match_scores_kernel(const float* __restri
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int p0 = blockIdx.x * MP;
     const int64_t t0 = (int64_t)blockIdx.y * MG;
-    const int64_t g_end = N;
     f32x4_t acc[4];
-#pragma unroll
-    for (int j = 0; j < 4; ++j) acc[j] = (f32x4_t){0.f, 0.f, 0.f, 0.f};
-    for (int d0 = 0; d0 < D; d0 += KC) {  // match_partial_kernel's tile, operation for operation
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            const int q = tid + 256 * i;
-            const int row = q >> 4, c4 = (q & 15) * 4;
-            float4 pv = make_float4(0.f, 0.f, 0.f, 0.f), gv = pv;
-            if (p0 + row < B && d0 + c4 < D) pv = *(const float4*)(P + (size_t)(p0 + row) * D + d0 + c4);
-            if (t0 + row < g_end && d0 + c4 < D) gv = *(const float4*)(G + (size_t)(t0 + row) * D + d0 + c4);
-            *(float4*)(sP + row * LD + c4) = pv;
-            *(float4*)(sG + row * LD + c4) = gv;
-        }
-        __syncthreads();
-#pragma unroll
-        for (int t16 = 0; t16 < KC / 16; ++t16) {
-            const int kof = 16 * t16 + 4 * (lane >> 4);
-            const float4 a4 = *(const float4*)(sP + (16 * wave + (lane & 15)) * LD + kof);
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                const float4 b4 = *(const float4*)(sG + (16 * j + (lane & 15)) * LD + kof);
-                acc[j] = __builtin_amdgcn_mfma_f32_16x16x4f32(a4.x, b4.x, acc[j], 0, 0, 0);
-                acc[j] = __builtin_amdgcn_mfma_f32_16x16x4f32(a4.y, b4.y, acc[j], 0, 0, 0);
-                acc[j] = __builtin_amdgcn_mfma_f32_16x16x4f32(a4.z, b4.z, acc[j], 0, 0, 0);
-                acc[j] = __builtin_amdgcn_mfma_f32_16x16x4f32(a4.w, b4.w, acc[j], 0, 0, 0);
-            }
-        }
-        __syncthreads();
-    }
+    score_tile_staged(P, B, p0, G, N, t0, D, sP, sG, acc);
     // acc[j][r] = score(probe 16 wave + 4 (lane >> 4) + r, row t0 + 16 j + (lane & 15))
 #pragma unroll
     for (int j = 0; j < 4; ++j)

@@ -9,8 +9,8 @@
 // reference's rule); and the N x N host matrix a duplicate-prototype scan of DatabaseBuilder's gallery needs.
 //
 // Scores are the exact f32 match path's, bit for bit: every output is the same v_mfma_f32_16x16x4f32
-// sequence as in match.hip / match_eval.hip (k = 16 t16 + 4 (lane >> 4) + c, c = 0..3 per t16; the main
-// loops are restated here).  Two passes over one split plan (match_split_plan's for the exact top-5) and a
+// sequence as in match.hip / match_eval.hip (k = 16 t16 + 4 (lane >> 4) + c, c = 0..3 per t16; the tile
+// loops are score_tile.h's).  Two passes over one split plan (match_split_plan's for the exact top-5) and a
 // scan between them:
 //   range_*_kernel<false>  count: 64 probes per block x one gallery split; one int32 per (probe, split)
 //                          into the workspace ws [n_split][B], a plain store (no atomics, no order-dependent
@@ -25,7 +25,8 @@
 // with `after`, index_base + j > after[b].  The last three matter: probe rows past B are zero probes and
 // rows past the split read as zeros, so both score 0.0, which passes any thresh <= 0.
 //
-// The D = 512 loop's counted waits and the fill pass's stores.  The loop waits `s_waitcnt vmcnt(8)` for the
+// The D = 512 loop's counted waits and the fill pass's stores (the loop is score_tile.h's p512_tile; this
+// paragraph is about what only this file adds to it).  The loop waits `s_waitcnt vmcnt(8)` for the
 // chunk it is about to read: three chunks of 4 LDS-DMAs are in flight, so "at most 8 outstanding" means the
 // oldest chunk has landed.  On gfx950 global stores count on the same counter.  The count is of outstanding
 // operations, and a wave's loads retire in issue order among themselves; the fill pass's stores are issued
@@ -35,18 +36,14 @@
 // wait stricter (it may also wait for part of the next chunk), never looser, so the wait counts stay as they
 // are; the cost is a possible stall after a tile with hits, which the timing in DESIGN.md bounds.  The fill
 // pass issues no global load inside the loop (offsets and `after` are read before the first DMA wait).
-#include "kernels.h"
+#include "score_tile.h"
 #include <limits.h>
 
 #include <algorithm>
 
 namespace fr {
+using namespace tile;
 namespace {
-
-constexpr int MP = 64;  // probes per block
-constexpr int MG = 64;  // gallery rows per tile
-constexpr int KC = 64;  // D chunk (floats)
-constexpr int LD = KC + 4;
 
 struct RangeArgs {
     const float* P;
@@ -135,7 +132,7 @@ __device__ __forceinline__ void range_finish_count(const RangeArgs& a, int p, in
     if (my_sub == 0 && e.live) a.ws[(size_t)blockIdx.y * a.B + p] = c;
 }
 
-// match_partial_kernel's main loop (any D % 4 == 0) with the range epilogue.
+// score_tile_staged (any D % 4 == 0) with the range epilogue.
 template <bool FILL>
 __global__ __launch_bounds__(256) void range_partial_kernel(const RangeArgs a) {
     __shared__ __attribute__((aligned(16))) float sPG[2 * MP * LD];
@@ -143,54 +140,18 @@ __global__ __launch_bounds__(256) void range_partial_kernel(const RangeArgs a) {
     float* sP = sPG;
     float* sG = sPG + MP * LD;
 
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int tid = threadIdx.x;
     const int p0 = blockIdx.x * MP;
     const int64_t g_begin = (int64_t)blockIdx.y * a.rows_per_split;
     const int64_t g_end = std::min<int64_t>(g_begin + a.rows_per_split, a.N);
-    const float* __restrict__ P = a.P;
-    const float* __restrict__ G = a.G;
-    const int B = a.B, D = a.D;
 
     const int my_p = tid >> 2, my_sub = tid & 3;
     RangeProbe e = range_probe_load<FILL>(a, p0 + my_p);
 
     for (int64_t t0 = g_begin; t0 < g_end; t0 += MG) {
         f32x4_t acc[4];
-#pragma unroll
-        for (int j = 0; j < 4; ++j) acc[j] = (f32x4_t){0.f, 0.f, 0.f, 0.f};
-        for (int d0 = 0; d0 < D; d0 += KC) {
-#pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                const int q = tid + 256 * i;
-                const int row = q >> 4, c4 = (q & 15) * 4;
-                float4 pv = make_float4(0.f, 0.f, 0.f, 0.f), gv = pv;
-                if (p0 + row < B && d0 + c4 < D) pv = *(const float4*)(P + (size_t)(p0 + row) * D + d0 + c4);
-                if (t0 + row < g_end && d0 + c4 < D) gv = *(const float4*)(G + (size_t)(t0 + row) * D + d0 + c4);
-                *(float4*)(sP + row * LD + c4) = pv;
-                *(float4*)(sG + row * LD + c4) = gv;
-            }
-            __syncthreads();
-#pragma unroll
-            for (int t16 = 0; t16 < KC / 16; ++t16) {
-                const int kof = 16 * t16 + 4 * (lane >> 4);
-                const float4 a4 = *(const float4*)(sP + (16 * wave + (lane & 15)) * LD + kof);
-#pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    const float4 b4 = *(const float4*)(sG + (16 * j + (lane & 15)) * LD + kof);
-                    acc[j] = __builtin_amdgcn_mfma_f32_16x16x4f32(a4.x, b4.x, acc[j], 0, 0, 0);
-                    acc[j] = __builtin_amdgcn_mfma_f32_16x16x4f32(a4.y, b4.y, acc[j], 0, 0, 0);
-                    acc[j] = __builtin_amdgcn_mfma_f32_16x16x4f32(a4.z, b4.z, acc[j], 0, 0, 0);
-                    acc[j] = __builtin_amdgcn_mfma_f32_16x16x4f32(a4.w, b4.w, acc[j], 0, 0, 0);
-                }
-            }
-            __syncthreads();
-        }
-        // acc[j][r] = score(probe 16 wave + 4 (lane >> 4) + r, gallery row t0 + 16 j + (lane & 15))
-#pragma unroll
-        for (int j = 0; j < 4; ++j)
-#pragma unroll
-            for (int r = 0; r < 4; ++r)
-                sS[(16 * wave + 4 * (lane >> 4) + r) * (MG + 1) + 16 * j + (lane & 15)] = acc[j][r];
+        score_tile_staged(a.P, a.B, p0, a.G, g_end, t0, a.D, sP, sG, acc);
+        store_score_tile(sS, acc);
         __syncthreads();
         range_tile<FILL>(a, sS, my_p, my_sub, (int)t0, (int)std::min<int64_t>(MG, g_end - t0), e);
         __syncthreads();
@@ -198,128 +159,38 @@ __global__ __launch_bounds__(256) void range_partial_kernel(const RangeArgs a) {
     if (!FILL) range_finish_count(a, p0 + my_p, my_sub, e);
 }
 
-// D = 512: match_p512_kernel's main loop -- the wave's 16 probes' A fragments in registers for the whole
-// split, gallery rows LDS-DMA'd in 64-row x 64-float chunks (16-B slots XOR-swizzled with the row) three
-// chunks ahead into a 4-buffer ring, counted vmcnt waits, one LDS-only barrier per chunk -- with the range
-// epilogue.  LDS: [4 chunks 64 KB][score tile 16.6 KB].
-constexpr int D512 = 512;
-constexpr int NBUF = 4;
-constexpr int CHUNK_B = MG * KC * 4;  // 16384
-constexpr int P512_LDS = NBUF * CHUNK_B + MP * (MG + 1) * 4;
-__device__ __forceinline__ void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
-
-// 16-B LDS-DMA (lane l lands at lds_addr + 16 l); the compiler does not see the LDS write, the kernel's own
-// counted waits cover it
-typedef int v4i32 __attribute__((ext_vector_type(4)));
-#pragma clang diagnostic push
-#pragma clang diagnostic ignored "-Winline-asm"
-__device__ __forceinline__ void dma16_asm(const v4i32& rsrc, uint32_t lds_addr, uint32_t voff) {
-    asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tbuffer_load_dwordx4 %0, %1, 0 offen lds"
-                 :
-                 : "v"(voff), "s"(rsrc), "s"(__builtin_amdgcn_readfirstlane(lds_addr))
-                 : "memory", "m0");
-}
-#pragma clang diagnostic pop
-
+// D = 512: the register-probe, LDS-DMA ring of score_tile.h (the p512_* pieces) with the range epilogue; the fill
+// pass's stores and the ring's counted waits: the file header.  LDS: [4 chunks 64 KB][score tile 16.6 KB].
 template <bool FILL>
 __global__ __launch_bounds__(256, 1) void range_p512_kernel(const RangeArgs a) {
     extern __shared__ __attribute__((aligned(16))) char smem[];  // [NBUF chunks][sS]
     float* sS = (float*)(smem + NBUF * CHUNK_B);
 
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int tid = threadIdx.x;
     const int p0 = blockIdx.x * MP;
     const int64_t g_begin = (int64_t)blockIdx.y * a.rows_per_split;
     const int64_t g_end = std::min<int64_t>(g_begin + a.rows_per_split, a.N);
     const int rows = (int)(g_end - g_begin);  // <= 64 tiles of 64 rows (the launcher's bound)
     const int ntiles = (rows + MG - 1) / MG;
-    const int B = a.B;
 
     const int my_p = tid >> 2, my_sub = tid & 3;
     RangeProbe e = range_probe_load<FILL>(a, p0 + my_p);
 
-    // the wave's A fragments: pa[t] = P[p0 + 16 wave + (lane & 15)][16 t + 4 (lane >> 4) .. + 3]
     float4 pa[D512 / 16];
-    {
-        const int p = p0 + 16 * wave + (lane & 15);
-        const float* src = a.P + (size_t)min(p, B - 1) * D512 + 4 * (lane >> 4);
-#pragma unroll
-        for (int t = 0; t < D512 / 16; ++t) pa[t] = *(const float4*)(src + 16 * t);
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // the DMA wait counts below see no earlier load
-        asm volatile("" : "+v"(e.after), "+v"(e.pos));    // (the probe's own loads are waited for here too)
-        const float z = p < B ? 1.f : 0.f;  // rows past the batch: zero probes (no branch around the loads)
-#pragma unroll
-        for (int t = 0; t < D512 / 16; ++t) pa[t] = make_float4(pa[t].x * z, pa[t].y * z, pa[t].z * z, pa[t].w * z);
-    }
-
-    // the split's rows as a buffer resource: rows past the split read 0 (out of range)
-    const uint64_t gp = (uint64_t)(a.G + (size_t)g_begin * D512);
-    const v4i32 gr = {(int)(uint32_t)gp, (int)((gp >> 32) & 0xffff), rows * D512 * 4, 0x00020000};
-    const uint32_t smem_base = (uint32_t)(uintptr_t)smem;
-    // chunk c = (tile c / 8, floats 64 (c % 8) ..) into ring buffer c % NBUF: wave w issues pieces w + 4u,
-    // piece q = rows 4q .. 4q + 3, lane -> row 4q + (lane >> 4), slot lane & 15 = column group
-    // (lane & 15) ^ (row & 15).  Chunks past the split are issued anyway (all out of range) so that every
-    // wait count is the same.
-    auto issue_chunk = [&](int c) {
-        const int t = c >> 3, d0 = (c & 7) * KC;
-#pragma unroll
-        for (int u = 0; u < 4; ++u) {
-            const int q = wave + 4 * u, row = 4 * q + (lane >> 4), g = (lane & 15) ^ (row & 15);
-            const uint32_t off = (uint32_t)((t * MG + row) * (D512 * 4) + (d0 + 4 * g) * 4);
-            dma16_asm(gr, smem_base + (c % NBUF) * CHUNK_B + q * 1024, off);
-        }
-    };
-#pragma unroll
-    for (int c = 0; c < NBUF - 1; ++c) issue_chunk(c);
+    p512_probes_load(a.P, a.B, p0, pa);
+    asm volatile("" : "+v"(e.after), "+v"(e.pos));  // the probe's own loads are waited for there too
+    p512_probes_mask(a.B, p0, pa);
+    const P512Ring ring = p512_ring_start(a.G + (size_t)g_begin * D512, rows, smem);
 
     for (int tl = 0; tl < ntiles; ++tl) {
         f32x4_t acc[4];
-#pragma unroll
-        for (int j = 0; j < 4; ++j) acc[j] = (f32x4_t){0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-        for (int ch = 0; ch < D512 / KC; ++ch) {
-            // chunk 8 tl + ch landed: at most 8 operations, so at most the two chunks issued after it, may
-            // be in flight (the fill pass's stores only make this stricter: the file header)
-            __builtin_amdgcn_sched_barrier(0);
-            asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
-            lds_barrier();
-            issue_chunk(8 * tl + ch + NBUF - 1);  // into the buffer read last chunk
-            const char* buf = smem + (ch % NBUF) * CHUNK_B;
-            // all 16 B fragments of the chunk first, one LDS wait, then the MFMAs with the 4 accumulators
-            // interleaved; per accumulator the order is x y z w per t16
-            float4 b4[KC / 16][4];
-#pragma unroll
-            for (int t16 = 0; t16 < KC / 16; ++t16) {
-                const int slot = (4 * t16 + (lane >> 4)) ^ (lane & 15);
-#pragma unroll
-                for (int j = 0; j < 4; ++j) b4[t16][j] = *(const float4*)(buf + (16 * j + (lane & 15)) * 256 + slot * 16);
-            }
-            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-            __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-            for (int t16 = 0; t16 < KC / 16; ++t16) {
-                const float4 a4 = pa[(KC / 16) * ch + t16];
-#pragma unroll
-                for (int j = 0; j < 4; ++j) acc[j] = __builtin_amdgcn_mfma_f32_16x16x4f32(a4.x, b4[t16][j].x, acc[j], 0, 0, 0);
-#pragma unroll
-                for (int j = 0; j < 4; ++j) acc[j] = __builtin_amdgcn_mfma_f32_16x16x4f32(a4.y, b4[t16][j].y, acc[j], 0, 0, 0);
-#pragma unroll
-                for (int j = 0; j < 4; ++j) acc[j] = __builtin_amdgcn_mfma_f32_16x16x4f32(a4.z, b4[t16][j].z, acc[j], 0, 0, 0);
-#pragma unroll
-                for (int j = 0; j < 4; ++j) acc[j] = __builtin_amdgcn_mfma_f32_16x16x4f32(a4.w, b4[t16][j].w, acc[j], 0, 0, 0);
-            }
-        }
+        p512_tile(ring, pa, smem, tl, acc);
         // scores -> LDS (its previous readers are 8 barriers back), then the range epilogue
-#pragma unroll
-        for (int j = 0; j < 4; ++j)
-#pragma unroll
-            for (int r = 0; r < 4; ++r)
-                sS[(16 * wave + 4 * (lane >> 4) + r) * (MG + 1) + 16 * j + (lane & 15)] = acc[j][r];
+        store_score_tile(sS, acc);
         lds_barrier();
         range_tile<FILL>(a, sS, my_p, my_sub, (int)(g_begin + (int64_t)tl * MG), min(MG, rows - tl * MG), e);
     }
-
-    // the trailing (out-of-range) DMAs land before the block ends
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    p512_ring_drain();
     if (!FILL) range_finish_count(a, p0 + my_p, my_sub, e);
 }
 
@@ -367,7 +238,7 @@ __global__ __launch_bounds__(SCAN_T) void range_scan_kernel(int B, int64_t* __re
 template <bool FILL>
 hipError_t launch_range_pass(const RangeArgs& a, hipStream_t s) {
     const dim3 grid((a.B + MP - 1) / MP, a.n_split);
-    if (a.D == D512 && a.rows_per_split <= 64 * MG) {  // (32-bit DMA offsets: at most 64 tiles per split)
+    if (a.D == D512 && a.rows_per_split <= P512_MAX_TILES * MG) {  // (32-bit DMA offsets: at most 64 tiles per split)
         if (hipError_t e = lds_opt_in((const void*)range_p512_kernel<FILL>, P512_LDS); e != hipSuccess) return e;
         hipLaunchKernelGGL(range_p512_kernel<FILL>, grid, dim3(256), P512_LDS, s, a);
     } else {

@@ -4,7 +4,7 @@
 // Replaces: models/facenet/facenet_dataloader.py:169-284 and models/facenet/facenet_model.py:53-115 (torch.cdist plus a
 // Python loop with a host synchronisation per (anchor, positive) pair) and train_facenet.py:41-54.
 //
-// Mining distances are the Gram form on exact f32 scores: match.hip's v_mfma_f32_16x16x4f32 tile loop (64 rows x 64
+// Mining distances are the Gram form on exact f32 scores: score_tile.h's v_mfma_f32_16x16x4f32 tile loop (64 rows x 64
 // rows, D staged through LDS in 64-float chunks, k = 16 t16 + 4 (lane >> 4) + c).
 //   count_kernel    per anchor the number of triplets (labels only) -> lims[a + 1];  scan_kernel: the prefix sums
 //   sqnorm_kernel   s[r] = sum_k e_rk^2 in a fixed order
@@ -18,7 +18,7 @@
 //   gather_kernel   one workgroup per dE row (and 1024-float D chunk): scans the index arrays and adds the row's terms in
 //                   ascending triplet order
 // No float atomics; every sum runs in an order fixed by the shapes; a band's height changes no bit.
-#include "kernels.h"
+#include "score_tile.h"
 #include "frhip.h"
 #include <float.h>
 #include <limits.h>
@@ -26,11 +26,9 @@
 #include <algorithm>
 
 namespace fr {
+using namespace tile;
 namespace {
 
-constexpr int MT = 64;  // rows per tile, both sides
-constexpr int KC = 64;  // D chunk (floats)
-constexpr int LD = KC + 4;
 constexpr float PAIR_EPS = 1e-6f;  // F.pairwise_distance's eps
 
 __global__ __launch_bounds__(256) void count_kernel(const int32_t* __restrict__ labels, int N, int mode,
@@ -77,65 +75,8 @@ __global__ __launch_bounds__(256) void sqnorm_kernel(const float* __restrict__ X
     const int lane = threadIdx.x & 63;
     const int r = blockIdx.x * 4 + (threadIdx.x >> 6);
     if (r >= R) return;
-    const float* x = X + (size_t)r * D;
-    float ss = 0.f;
-    for (int d = 4 * lane; d < D; d += 256) {
-        const float4 v = *(const float4*)(x + d);
-        ss += v.x * v.x;
-        ss += v.y * v.y;
-        ss += v.z * v.z;
-        ss += v.w * v.w;
-    }
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) ss += __shfl_xor(ss, o);
+    const float ss = row_sqsum(X + (size_t)r * D, D);
     if (lane == 0) sq[r] = ss;
-}
-
-// acc[j][r] = sum_d X[x0 + 16 wave + 4 (lane >> 4) + r][d] Y[t0 + 16 j + (lane & 15)][d]; rows past rx / ry and
-// columns past D read as zero (arcmargin.hip's score_tile).
-__device__ __forceinline__ void score_tile(const float* __restrict__ X, int64_t rx, int64_t x0, const float* __restrict__ Y,
-                                           int64_t ry, int64_t t0, int D, float* sX, float* sY, f32x4_t (&acc)[4]) {
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-#pragma unroll
-    for (int j = 0; j < 4; ++j) acc[j] = (f32x4_t){0.f, 0.f, 0.f, 0.f};
-    // chunk d0 + KC is loaded into registers while chunk d0's MFMAs run
-    float4 xv[4], yv[4];
-    auto load = [&](int d0) {
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            const int q = tid + 256 * i;
-            const int row = q >> 4, c4 = (q & 15) * 4;
-            xv[i] = yv[i] = make_float4(0.f, 0.f, 0.f, 0.f);
-            if (x0 + row < rx && d0 + c4 < D) xv[i] = *(const float4*)(X + (size_t)(x0 + row) * D + d0 + c4);
-            if (t0 + row < ry && d0 + c4 < D) yv[i] = *(const float4*)(Y + (size_t)(t0 + row) * D + d0 + c4);
-        }
-    };
-    load(0);
-    for (int d0 = 0; d0 < D; d0 += KC) {
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            const int q = tid + 256 * i;
-            const int row = q >> 4, c4 = (q & 15) * 4;
-            *(float4*)(sX + row * LD + c4) = xv[i];
-            *(float4*)(sY + row * LD + c4) = yv[i];
-        }
-        __syncthreads();
-        if (d0 + KC < D) load(d0 + KC);
-#pragma unroll
-        for (int t16 = 0; t16 < KC / 16; ++t16) {
-            const int kof = 16 * t16 + 4 * (lane >> 4);
-            const float4 a4 = *(const float4*)(sX + (16 * wave + (lane & 15)) * LD + kof);
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                const float4 b4 = *(const float4*)(sY + (16 * j + (lane & 15)) * LD + kof);
-                acc[j] = __builtin_amdgcn_mfma_f32_16x16x4f32(a4.x, b4.x, acc[j], 0, 0, 0);
-                acc[j] = __builtin_amdgcn_mfma_f32_16x16x4f32(a4.y, b4.y, acc[j], 0, 0, 0);
-                acc[j] = __builtin_amdgcn_mfma_f32_16x16x4f32(a4.z, b4.z, acc[j], 0, 0, 0);
-                acc[j] = __builtin_amdgcn_mfma_f32_16x16x4f32(a4.w, b4.w, acc[j], 0, 0, 0);
-            }
-        }
-        __syncthreads();
-    }
 }
 
 // band[i - b0][j] = d_ij for anchors i in [b0, b1) and every row j; block (x, y) = (64-row tile of j, 64-anchor tile).
@@ -145,7 +86,7 @@ __global__ __launch_bounds__(256) void dist_kernel(const float* __restrict__ E, 
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int x0 = b0 + blockIdx.y * MT, t0 = blockIdx.x * MT;
     f32x4_t acc[4];
-    score_tile(E, b1, x0, E, N, t0, D, sXY, sXY + MT * LD, acc);
+    score_tile_prefetch<int64_t, int64_t>(E, b1, x0, E, N, t0, D, sXY, sXY + MT * LD, acc);
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
         const int i = x0 + 16 * wave + 4 * (lane >> 4) + r;

@@ -4,10 +4,10 @@
 // Replaces: models/arcface/train_arcface.py:114-210 and models/facenet/train_facenet.py:64-160 (a Python loop with one
 // np.dot per sampled pair, unseeded).
 //
-// Scores are exact f32: match.hip's v_mfma_f32_16x16x4f32 tile loop (64 rows x 64 rows, D staged through LDS in
+// Scores are exact f32: score_tile.h's v_mfma_f32_16x16x4f32 tile loop (64 rows x 64 rows, D staged through LDS in
 // 64-float chunks, k = 16 t16 + 4 (lane >> 4) + c), then s = (g r_i) r_j with r = 1 / (sqrt(sum e^2) + 1e-8) (r = 1
 // without normalisation).  No N x N matrix is stored.
-//   prep_kernel     r[i] (sqnorm_kernel's summation order, IEEE square root and division); zeroes counts and totals
+//   prep_kernel     r[i] (score_tile.h's row_sqsum, IEEE square root and division); zeroes counts and totals
 //   sweep_kernel    workgroup (row tile, column chunk): 64 rows x the chunk's VCHUNK columns, tiles in ascending j.
 //                   Per-row state (sums, best / worst mate, best impostor) in registers, a lane owns the columns
 //                   = its lane & 15 (mod 16) of its 4 rows; at the chunk's end a 16-lane tree, then one partial per
@@ -16,7 +16,7 @@
 //   combine_kernel  one thread per row: the chunk partials in ascending chunk order -> row_score, row_idx, row_sum
 // The chunk width is a constant, so every float sum's order is fixed by (N, D): the band of rows one launch covers
 // (what the workspace holds) changes no bit.  Without row outputs the tiles below the diagonal are skipped.
-#include "kernels.h"
+#include "score_tile.h"
 #include "frhip.h"
 #include <float.h>
 #include <limits.h>
@@ -24,18 +24,16 @@
 #include <algorithm>
 
 namespace fr {
+using namespace tile;
 namespace {
 
-constexpr int MT = 64;  // rows per tile, both sides
-constexpr int KC = 64;  // D chunk (floats)
-constexpr int LD = KC + 4;
 constexpr int VCHUNK = 1024;  // columns per partial: 16 tiles
 constexpr int PART_B = 32;    // bytes of partials per (row, chunk): 2 sums, 3 scores, 3 indices
 
 int pad64(int n) { return (n + 63) / 64 * 64; }
 int n_chunks(int N) { return (N + VCHUNK - 1) / VCHUNK; }
 
-// r[i] = 1 / (sqrt(sum_k e_ik^2) + 1e-8), the square sum in triplet.hip's sqnorm_kernel's order; 1 when !normalize.
+// r[i] = 1 / (sqrt(sum_k e_ik^2) + 1e-8), the square sum by score_tile.h's row_sqsum; 1 when !normalize.
 __global__ __launch_bounds__(256) void prep_kernel(const float* __restrict__ X, int R, int D, int normalize,
                                                    float* __restrict__ rinv, unsigned long long* __restrict__ counts,
                                                    int T, unsigned long long* __restrict__ totals) {
@@ -50,65 +48,8 @@ __global__ __launch_bounds__(256) void prep_kernel(const float* __restrict__ X, 
         if (lane == 0) rinv[r] = 1.f;
         return;
     }
-    const float* x = X + (size_t)r * D;
-    float ss = 0.f;
-    for (int d = 4 * lane; d < D; d += 256) {
-        const float4 v = *(const float4*)(x + d);
-        ss += v.x * v.x;
-        ss += v.y * v.y;
-        ss += v.z * v.z;
-        ss += v.w * v.w;
-    }
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) ss += __shfl_xor(ss, o);
+    const float ss = row_sqsum(X + (size_t)r * D, D);
     if (lane == 0) rinv[r] = __fdiv_rn(1.f, __fadd_rn(__fsqrt_rn(ss), 1e-8f));
-}
-
-// acc[j][r] = sum_d X[x0 + 16 wave + 4 (lane >> 4) + r][d] X[t0 + 16 j + (lane & 15)][d]; rows past n and columns
-// past D read as zero (triplet.hip's score_tile with both sides from one matrix).
-__device__ __forceinline__ void score_tile(const float* __restrict__ X, int n, int x0, int t0, int D, float* sX, float* sY,
-                                           f32x4_t (&acc)[4]) {
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-#pragma unroll
-    for (int j = 0; j < 4; ++j) acc[j] = (f32x4_t){0.f, 0.f, 0.f, 0.f};
-    // chunk d0 + KC is loaded into registers while chunk d0's MFMAs run
-    float4 xv[4], yv[4];
-    auto load = [&](int d0) {
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            const int q = tid + 256 * i;
-            const int row = q >> 4, c4 = (q & 15) * 4;
-            xv[i] = yv[i] = make_float4(0.f, 0.f, 0.f, 0.f);
-            if (x0 + row < n && d0 + c4 < D) xv[i] = *(const float4*)(X + (size_t)(x0 + row) * D + d0 + c4);
-            if (t0 + row < n && d0 + c4 < D) yv[i] = *(const float4*)(X + (size_t)(t0 + row) * D + d0 + c4);
-        }
-    };
-    load(0);
-    for (int d0 = 0; d0 < D; d0 += KC) {
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            const int q = tid + 256 * i;
-            const int row = q >> 4, c4 = (q & 15) * 4;
-            *(float4*)(sX + row * LD + c4) = xv[i];
-            *(float4*)(sY + row * LD + c4) = yv[i];
-        }
-        __syncthreads();
-        if (d0 + KC < D) load(d0 + KC);
-#pragma unroll
-        for (int t16 = 0; t16 < KC / 16; ++t16) {
-            const int kof = 16 * t16 + 4 * (lane >> 4);
-            const float4 a4 = *(const float4*)(sX + (16 * wave + (lane & 15)) * LD + kof);
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                const float4 b4 = *(const float4*)(sY + (16 * j + (lane & 15)) * LD + kof);
-                acc[j] = __builtin_amdgcn_mfma_f32_16x16x4f32(a4.x, b4.x, acc[j], 0, 0, 0);
-                acc[j] = __builtin_amdgcn_mfma_f32_16x16x4f32(a4.y, b4.y, acc[j], 0, 0, 0);
-                acc[j] = __builtin_amdgcn_mfma_f32_16x16x4f32(a4.z, b4.z, acc[j], 0, 0, 0);
-                acc[j] = __builtin_amdgcn_mfma_f32_16x16x4f32(a4.w, b4.w, acc[j], 0, 0, 0);
-            }
-        }
-        __syncthreads();
-    }
 }
 
 struct VerifyArgs {
@@ -184,7 +125,7 @@ __global__ __launch_bounds__(256) void sweep_kernel(const VerifyArgs a) {
 
     for (int t0 = t_begin; t0 < c1; t0 += MT) {
         f32x4_t acc[4];
-        score_tile(a.E, N, x0, t0, a.D, sXY, sXY + MT * LD, acc);
+        score_tile_prefetch(a.E, N, x0, a.E, N, t0, a.D, sXY, sXY + MT * LD, acc);
         int cj[4], lj[4];
         float rj[4];
         bool jv[4];

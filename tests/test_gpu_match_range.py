@@ -166,6 +166,36 @@ def test_float_inputs_equal_the_exact_scores(gpu, B, N, d):
         assert np.array_equal(s[l[b]:l[b + 1]].view(np.uint32), s_all[b][keep][o].view(np.uint32)), b
 
 
+# 3b
+def test_float_multi_tile_splits_equal_one_tile_shards(gpu):
+    """D = 512 float inputs with two tiles per split (the chunk ring wraps from tile to tile and into a ragged
+    last tile) against the same rows installed as shards of 1000 rows, one tile per split each: with
+    thresh = -inf every score comes back, so the whole-gallery CSR must be, bit for bit in scores and exactly
+    in indices, the per-probe concatenation of the shards' CSRs."""
+    from facerecognition_amd import _native as NL
+    from facerecognition_amd.gallery import DeviceGallery
+
+    B, N, SHARD = 70, 8269, 1000
+    G, P, _ = float_case(11, B, N, 512)
+    t = float("-inf")
+    whole = DeviceGallery(G)
+    tiles = (N + 63) // 64
+    assert 2 * NL.lib().fr_debug_match_range_splits(whole._h, B) == tiles  # two tiles per split
+    l, s, i = run(whole, P, t)
+    assert np.array_equal(l, np.arange(B + 1) * N)
+    s, i = s.reshape(B, N), i.reshape(B, N)
+    for base in range(0, N, SHARD):
+        n = min(SHARD, N - base)
+        shard = DeviceGallery(G[base:base + n], index_base=base)
+        assert NL.lib().fr_debug_match_range_splits(shard._h, B) == (n + 63) // 64  # one tile per split
+        sl, ss, si = run(shard, P, t)
+        assert np.array_equal(sl, np.arange(B + 1) * n)
+        assert np.array_equal(si.reshape(B, n), i[:, base:base + n]), base
+        assert np.array_equal(ss.reshape(B, n).view(np.uint32), s[:, base:base + n].view(np.uint32)), base
+        shard.close()
+    assert np.array_equal(i, np.broadcast_to(np.arange(N), (B, N)))
+
+
 # 4
 def test_capacity_truncates_at_the_end(cases):
     c = cases["splits"]
