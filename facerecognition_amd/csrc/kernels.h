@@ -494,4 +494,10 @@ hipError_t launch_head_train_backward(HeadArgs a, const float* gamma2, const flo
                                       const float* Z, const float* dY, float* dX, float* dW, float* dbias, float* dgamma1,
                                       float* dbeta1, float* dgamma2, float* dbeta2, void* ws, hipStream_t s);
 
+// Augmentation (augment.hip; DESIGN.md §4 "Augmentation").  Arguments are checked by augment_api.cpp; ops, args and norm
+// are device arrays here.  augment_lds_bytes is the dynamic LDS of one workgroup.
+size_t augment_lds_bytes(int H, int W);
+hipError_t launch_augment(const uint8_t* in, int B, int H, int W, const int32_t* ops, const double* args, int n_ops,
+                          const float* norm, float* out_f32, uint8_t* out_u8, hipStream_t s);
+
 }  // namespace fr

@@ -502,6 +502,70 @@ int fr_verify_pairs(const float* E, int N, int D, const int32_t* labels, int nor
                     float* row_score /*[N][3], NULL*/, int32_t* row_idx /*[N][3], NULL*/,
                     float* row_sum /*[N][2], NULL*/, void* ws, size_t ws_bytes, void* stream);
 
+/* ---- Augmentation: the training transforms of the reference's dataloaders (torchvision on PIL images) as a per-image
+ *      op list run on the device, one workgroup per image with the image resident in LDS.  Handle-free, caller-owned
+ *      device buffers.  in (device u8) [B][H][W][3].  ops (HOST i32) [B][n_ops] and args (HOST f64) [B][n_ops][8] are
+ *      read and checked before the call returns, then staged into ws and the kernel is enqueued on the stream.
+ *      Image b runs ops[b][0 .. n_ops) in order on its u8 image (Pillow's arithmetic unless stated; the restatement and
+ *      its checks against Pillow are tests/augment_ref.py and tests/test_augment_ref.py):
+ *        FR_AUG_NOP                   nothing (pads a row)
+ *        FR_AUG_FLIP_H                transpose(FLIP_LEFT_RIGHT)
+ *        FR_AUG_AFFINE_NEAREST        Image.transform(size, AFFINE, m, NEAREST), fill 0, as Pillow's 16.16 fixed-point
+ *                                     walk: FIX(v) = floor(65536 v + 0.5), source x = (FIX(m2 + m0/2 + m1/2) + FIX(m1) y
+ *                                     + FIX(m0) x) >> 16, y likewise from m3..m5.  args m0..m5 (output -> input map).
+ *                                     As Pillow requires for this walk, |m0 x + m1 y + m2| and |m3 x + m4 y + m5| must be
+ *                                     < 32768 at (0,0), (W,0), (0,H), (W,H).  (Pillow answers m1 = m3 = 0 from another
+ *                                     routine that steps in double; here every matrix takes the fixed-point walk.)
+ *        FR_AUG_PERSPECTIVE_BILINEAR  Image.transform(size, PERSPECTIVE, a, BILINEAR), fill 0: double arithmetic at
+ *                                     (x + 0.5, y + 0.5), truncating store; a source outside [0,W) x [0,H) or NaN is 0.
+ *                                     args a0..a7.
+ *        FR_AUG_CROP_RESIZE           crop((j, i, j + w, i + h)).resize((W, H), BILINEAR): the two-pass antialiased
+ *                                     resampler of fr_resize_u8 with per-image 22-bit coefficients.  args i, j, h, w:
+ *                                     integers, 1 <= h, 1 <= w, the box inside the image.
+ *        FR_AUG_BRIGHTNESS / FR_AUG_CONTRAST / FR_AUG_SATURATION   ImageEnhance.{Brightness, Contrast, Color}.enhance(f):
+ *                                     t = d + (float)f (src - d) in f32 against d = 0 / the constant int(mean(L) + 0.5) /
+ *                                     L, truncated for 0 <= f <= 1, else clipped to [0, 255] first;
+ *                                     L = (19595 R + 38470 G + 7471 B + 0x8000) >> 16.  args f >= 0.
+ *        FR_AUG_HUE                   torchvision's PIL adjust_hue: convert("HSV"), H += (uint8)(int)(255 f) with u8 wrap,
+ *                                     convert back.  args f in [-0.5, 0.5].
+ *        FR_AUG_GRAYSCALE             convert("L") in all 3 channels
+ *        FR_AUG_GAUSS_BLUR            torchvision's tensor gaussian_blur of a u8 image: taps (float)w[dy] (float)w[dx]
+ *                                     (one f32 product), reflect padding, the f32 sum from 0 in row-major tap order,
+ *                                     every product rounded, rintf, clamp to [0, 255].  args k, w[0 .. k): k in {3, 5, 7},
+ *                                     k / 2 < min(H, W).
+ *        FR_AUG_ERASE                 RandomErasing(value = 0): the box of out_f32 is 0.0f; out_u8 is not touched.  args
+ *                                     i, j, h, w as for the crop.  At most one per row, and only FR_AUG_NOP after it.
+ *      Outputs (either may be NULL, not both): out_f32 [B][3][H][W] = ToTensor + Normalize(0.5, 0.5) of the result,
+ *      ((float)u / 255.0f - 0.5f) / 0.5f per byte u (what fr_embed takes as FR_IN_F32_NCHW); out_u8 [B][H][W][3].
+ *      No atomics and no randomness: the result is a pure function of (in, ops, args), bitwise repeatable.
+ *      Limits, each FR_ERR_ARG with a message before any HIP call: B >= 1 (B <= 2^24), H, W >= 1 with
+ *      6 H W <= 153600 and H + W <= 512 (the two LDS image buffers and the coefficient tables: 160 x 160 is the largest
+ *      square), 0 <= n_ops <= 16, in, ws, and (when n_ops > 0) ops and args non-null, an output non-null, known opcodes,
+ *      every argument of every row finite, the per-op limits above, ws_bytes >= fr_augment_workspace. ---- */
+#define FR_AUGMENT_MAX_OPS 16
+#define FR_AUGMENT_ARGS 8
+#define FR_AUG_NOP 0
+#define FR_AUG_FLIP_H 1
+#define FR_AUG_AFFINE_NEAREST 2
+#define FR_AUG_PERSPECTIVE_BILINEAR 3
+#define FR_AUG_CROP_RESIZE 4
+#define FR_AUG_BRIGHTNESS 5
+#define FR_AUG_CONTRAST 6
+#define FR_AUG_SATURATION 7
+#define FR_AUG_HUE 8
+#define FR_AUG_GRAYSCALE 9
+#define FR_AUG_GAUSS_BLUR 10
+#define FR_AUG_ERASE 11
+
+/* Bytes of device workspace fr_augment needs (the staged op lists and the normalisation table); 0 and a message on
+ * bad arguments. */
+size_t fr_augment_workspace(int B, int n_ops);
+/* Stream-ordered.  The host arrays may be reused as soon as the call returns; the call may wait for the staging copy of
+ * the previous fr_augment call on the same device. */
+int fr_augment(const uint8_t* in, int B, int H, int W, const int32_t* ops /*host [B][n_ops]*/,
+               const double* args /*host [B][n_ops][8]*/, int n_ops, float* out_f32 /*[B][3][H][W], NULL*/,
+               uint8_t* out_u8 /*[B][H][W][3], NULL*/, void* ws, size_t ws_bytes, void* stream);
+
 /* ---- Head training: the embedding head between a frozen trunk and the losses above, forward and backward
  *      (ArcFaceModel's bn1 -> dropout -> fc -> bn2, IResNet100's bn2 -> flatten -> fc -> features, FaceNet's
  *      dropout -> last_linear -> last_bn).  Handle-free, caller-owned f32 device buffers; X, W, Y, dW, dX (and A, Z, dY)
