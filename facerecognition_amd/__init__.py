@@ -41,6 +41,9 @@ def __getattr__(name):  # lazy: importing the package must not initialise the GP
     if name in _HEAD:
         from . import head
         return getattr(head, name)
+    if name in _BACKBONE_TRAIN:
+        from . import backbone_train
+        return getattr(backbone_train, name)
     if name in _AUGMENT:
         from . import augment
         return getattr(augment, name)
@@ -49,6 +52,7 @@ def __getattr__(name):  # lazy: importing the package must not initialise the GP
 
 _AUGMENT = ("get_train_transforms", "get_val_transforms", "facenet_train_transforms", "DeviceTransform", "mixup_data")
 _HEAD = ("EmbeddingHead",)
+_BACKBONE_TRAIN = ("Bottleneck", "ResNet50Layer4")
 _VERIFICATION = ("verify_pairs", "compute_verification_accuracy", "verification_report")
 _TRIPLET = ("TripletLoss", "mine_triplets", "mine_semi_hard_triplets", "mine_batch_hard_triplets", "triplet_loss",
             "online_triplet_loss", "compute_triplet_metrics")

@@ -27,6 +27,10 @@ FR_EMBED_RAW = 1
 FR_EMBED_ASYNC = 2
 FR_HEAD_BATCH_STATS = 1
 FR_HEAD_DROPOUT = 2
+FR_CONV_IN_RELU = 1
+FR_BN_BATCH_STATS = 1
+FR_BN_RELU = 2
+FR_CUT_LAYER4_IN = 0
 FR_ERR_STAGE = -6
 FR_TILE_BAND = 7
 FR_TILE_IMG28 = 10
@@ -191,6 +195,18 @@ _SIGS = {
                                  ctypes.c_float, ctypes.c_uint64, ctypes.c_uint64, c_void_p, c_void_p, c_void_p, c_void_p,
                                  c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                  c_void_p, c_size_t, c_void_p]),
+    "fr_features_at_shape": (c_int, [c_void_p, c_int, ctypes.POINTER(c_int), ctypes.POINTER(c_int), ctypes.POINTER(c_int)]),
+    "fr_features_at": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
+    "fr_conv_train_workspace": (c_size_t, [c_int, c_int, c_int, c_int, c_int, c_int, c_int]),
+    "fr_conv_train_forward": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p, c_int,
+                                      c_int, c_int, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "fr_conv_train_backward": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p, c_int,
+                                       c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "fr_bn2d_train_stats": (c_int, [c_void_p, c_int64, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int,
+                                    ctypes.c_float, ctypes.c_float, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "fr_bn_act_forward": (c_int, [c_void_p, c_int64, c_int, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p]),
+    "fr_bn_act_backward": (c_int, [c_void_p, c_void_p, c_int64, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                   c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "fr_augment_workspace": (c_size_t, [c_int, c_int]),
     "fr_augment": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p,
                            c_size_t, c_void_p]),

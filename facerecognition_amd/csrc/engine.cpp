@@ -769,6 +769,7 @@ void build_resnet50(Builder& b) {
             ch.out = x;
             b.close_stage(ch_op, ch);
         }
+        if (l == 2) h->cut_l4in = x;  // fr_features_at: what layer4.0.conv1 and layer4.0.downsample read
     }
     h->ex_tensor = x;  // fr_explain: Grad-CAM on backbone.layer4 (the avg-pool's input)
     h->ex_layout = 0;
@@ -1817,6 +1818,7 @@ int fr_load_weights(fr_handle* h, const void* blob, size_t nbytes) {
     h->ops.clear();
     h->loaded = false;
     h->ex_tensor = h->ex_conv = -1;
+    h->cut_l4in = -1;
     Builder b{h, W};
     if (h->arch == FR_ARCH_IRESNET100) build_iresnet100(b);
     else if (h->arch == FR_ARCH_RESNET50_ARCFACE) build_resnet50(b);
@@ -2108,6 +2110,56 @@ int fr_features(fr_handle* h, const void* in, int in_fmt, int B, int H, int W, f
     const int rc = embed_locked(h, in, in_fmt, B, H, W, h->ex_emb, FR_EMBED_RAW, stream);
     if (rc) return rc;
     FR_HIP_CHECK(launch_features_cvt(t.dev, B, P, t.C, h->dtype == FR_DTYPE_F16 || t.f16, out, (hipStream_t)stream));
+    return FR_OK;
+}
+
+int fr_features_at_shape(const fr_handle* h, int cut, int* th, int* tw, int* tc) {
+    if (!h || !th || !tw || !tc) { set_error("fr_features_at_shape: null argument"); return FR_ERR_ARG; }
+    if (cut != FR_CUT_LAYER4_IN) { set_error("fr_features_at_shape: unknown cut"); return FR_ERR_ARG; }
+    if (h->arch != FR_ARCH_RESNET50_ARCFACE) {
+        set_error("fr_features_at_shape: FR_CUT_LAYER4_IN exists for resnet50_arcface only");
+        return FR_ERR_ARG;
+    }
+    if (!h->loaded || h->cut_l4in < 0) { set_error("fr_features_at_shape: weights not loaded"); return FR_ERR_STATE; }
+    const auto& t = h->tensors[h->cut_l4in];
+    *th = t.H; *tw = t.W; *tc = t.C;
+    return FR_OK;
+}
+
+int fr_features_at(fr_handle* h, const void* in, int in_fmt, int B, int H, int W, int cut, float* out, void* stream) {
+    if (!h) { set_error("fr_features_at: null handle"); return FR_ERR_ARG; }
+    std::lock_guard<std::mutex> lk(h->mu);
+    if (cut != FR_CUT_LAYER4_IN) { set_error("fr_features_at: unknown cut"); return FR_ERR_ARG; }
+    if (h->arch != FR_ARCH_RESNET50_ARCFACE) {
+        set_error("fr_features_at: FR_CUT_LAYER4_IN exists for resnet50_arcface only");
+        return FR_ERR_ARG;
+    }
+    if (h->dtype == FR_DTYPE_FP8) { set_error("fr_features_at: not available on an FR_DTYPE_FP8 handle"); return FR_ERR_ARG; }
+    if (!h->loaded || h->cut_l4in < 0) { set_error("fr_features_at: weights not loaded"); return FR_ERR_STATE; }
+    if (!in || !out || B <= 0) { set_error("fr_features_at: bad argument"); return FR_ERR_ARG; }
+    if (h->max_batch <= 0 || !h->ex_emb) {
+        set_error("fr_features_at: nothing reserved (call fr_reserve first)");
+        return FR_ERR_STATE;
+    }
+    if (B > h->max_batch) {
+        set_error("fr_features_at: B = " + std::to_string(B) + " is above the reserved batch " +
+                  std::to_string(h->max_batch) + " (fr_reserve)");
+        return FR_ERR_ARG;
+    }
+    if (B > embed_chunk(h)) {  // a chunked forward leaves only its last chunk's activations behind
+        set_error("fr_features_at: B is above the largest single forward (" + std::to_string(embed_chunk(h)) + ")");
+        return FR_ERR_ARG;
+    }
+    const auto& t = h->tensors[h->cut_l4in];
+    if (t.C % 8) { set_error("fr_features_at: the cut tensor's channels are no multiple of 8"); return FR_ERR_ARG; }
+    // The whole forward runs and is waited for (fr_features' rules).  Every plan tensor has an allocation of its own
+    // (reserve()), so nothing after the cut overwrites it; and it is a tensor the per-conv ops layer4.0.conv1 and
+    // layer4.0.downsample read, so whichever of the layer3 chain stage or its member convs ran has written it as plain
+    // 16-bit NHWC (the chain's own layouts stay inside the launch).
+    const int rc = embed_locked(h, in, in_fmt, B, H, W, h->ex_emb, FR_EMBED_RAW, stream);
+    if (rc) return rc;
+    FR_HIP_CHECK(launch_features_cvt(t.dev, B * t.H * t.W, 1, t.C, h->dtype == FR_DTYPE_F16 || t.f16, out,
+                                     (hipStream_t)stream));
     return FR_OK;
 }
 

@@ -214,6 +214,7 @@ struct fr_handle {
     // of reserve(): the score gradient [max_batch][embed_dim], the head-input gradient [max_batch][head Kpad] and
     // the raw embeddings when the caller takes none
     int ex_tensor = -1, ex_layout = 0, ex_conv = -1;
+    int cut_l4in = -1;  // fr_features_at(FR_CUT_LAYER4_IN): the tensor layer4.0 reads (ResNet-50 only)
     float* ex_g = nullptr;
     float* ex_v = nullptr;
     float* ex_emb = nullptr;

@@ -494,6 +494,28 @@ hipError_t launch_head_train_backward(HeadArgs a, const float* gamma2, const flo
                                       const float* Z, const float* dY, float* dX, float* dW, float* dbias, float* dgamma1,
                                       float* dbeta1, float* dgamma2, float* dbeta2, void* ws, hipStream_t s);
 
+// Backbone training (conv_train.hip; DESIGN.md §4 "Backbone training: layer4").  Arguments are checked by
+// conv_train_api.cpp; every launcher only enqueues on s.
+struct ConvTrainArgs {
+    const float* X;              // [B][H][W][Cin]
+    const float* Wt;             // [Cout][k][k][Cin]
+    const float *scale, *shift;  // [Cin]: the input transform A = relu?(X scale + shift), or both null (A = X)
+    bool relu;
+    int B, H, W, Cin, Cout, k, stride, pad, OH, OW;
+};
+size_t conv_train_workspace(const ConvTrainArgs& a);
+hipError_t launch_conv_train_forward(const ConvTrainArgs& a, float* Z, void* ws, hipStream_t s);
+hipError_t launch_conv_train_backward(const ConvTrainArgs& a, const float* dZ, float* dA, float* dW, hipStream_t s);
+hipError_t launch_bn2d_train_stats(const float* Z, int64_t M, int C, const float* gamma, const float* beta, float* rm,
+                                   float* rv, bool batch, float eps, float momentum, float* mean, float* rstd, float* scale,
+                                   float* shift, hipStream_t s);
+hipError_t launch_bn_act_forward(const float* Z, int64_t M, int C, const float* scale, const float* shift, const float* Res,
+                                 bool relu, float* Y, hipStream_t s);
+hipError_t launch_bn_act_backward(const float* dY, const float* Z, int64_t M, int C, bool batch, bool relu,
+                                  const float* gamma, const float* mean, const float* rstd, const float* scale,
+                                  const float* shift, const float* Res, float* dZ, float* dRes, float* dgamma, float* dbeta,
+                                  hipStream_t s);
+
 // Augmentation (augment.hip; DESIGN.md §4 "Augmentation").  Arguments are checked by augment_api.cpp; ops, args and norm
 // are device arrays here.  augment_lds_bytes is the dynamic LDS of one workgroup.
 size_t augment_lds_bytes(int H, int W);

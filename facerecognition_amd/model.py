@@ -123,14 +123,27 @@ class FRModel:
         N.check(k if k < 0 else 0, "fr_features_dim")
         return k
 
-    def features(self, x):
+    def features(self, x, at=None):
         """Device f32 [B, K] input of the embedding head in torch's flatten order (fr_features): one forward, then
-        the 16-bit activations the engine's own head reads, converted.  Feeds facerecognition_amd.head.EmbeddingHead."""
+        the 16-bit activations the engine's own head reads, converted.  Feeds facerecognition_amd.head.EmbeddingHead.
+
+        at="layer4_in" (resnet50_arcface): the tensor backbone.layer4 reads instead, physical NHWC [B, 7, 7, 1024]
+        (fr_features_at), which feeds facerecognition_amd.backbone_train.ResNet50Layer4."""
         import torch
 
+        if at not in (None, "layer4_in"):
+            raise ValueError(f"features: at must be None or 'layer4_in', got {at!r}")
         x, fmt, H, W = self._prep(x)
         B = int(x.shape[0])
         self.reserve(B)  # fr_features takes no batch above the reserved one (a no-op once reserved)
+        if at == "layer4_in":
+            h, w, c = ctypes.c_int(), ctypes.c_int(), ctypes.c_int()
+            N.check(N.lib().fr_features_at_shape(self._h, N.FR_CUT_LAYER4_IN, ctypes.byref(h), ctypes.byref(w),
+                                                 ctypes.byref(c)), "fr_features_at_shape")
+            out = torch.empty((B, h.value, w.value, c.value), dtype=torch.float32, device=self.device)
+            N.check(N.lib().fr_features_at(self._h, N.ptr(x), fmt, B, H, W, N.FR_CUT_LAYER4_IN, N.ptr(out),
+                                           N.stream_ptr(self.device)), "fr_features_at")
+            return out
         out = torch.empty((B, self.feature_dim), dtype=torch.float32, device=self.device)
         N.check(N.lib().fr_features(self._h, N.ptr(x), fmt, B, H, W, N.ptr(out), N.stream_ptr(self.device)),
                 "fr_features")

@@ -130,6 +130,16 @@ int fr_features_dim(const fr_handle* h);
  * activations the engine's own head reads, converted to f32.  This is the input of fr_head_forward. */
 int fr_features(fr_handle* h, const void* in, int in_fmt, int B, int H, int W, float* out, void* stream);
 
+/* A tensor inside the trunk, for training what comes after it ("Backbone training" below).  cut = FR_CUT_LAYER4_IN:
+ * the output of backbone.layer3.5, which layer4.0.conv1 and layer4.0.downsample.0 read, as device f32 physical NHWC
+ * out [B][h][w][c] ([B][7][7][1024] for a 112 x 112 input; fr_features_at_shape gives h, w, c).  resnet50_arcface
+ * handles only, and not FR_DTYPE_FP8 ones: anything else is FR_ERR_ARG.  fr_features' rules otherwise: one whole
+ * forward, waited for, B at most the reserved batch and at most one chunk; the values are the engine's 16-bit
+ * activations converted to f32, whichever of the fused layer3 chain or its member convs the plan ran. */
+#define FR_CUT_LAYER4_IN 0
+int fr_features_at_shape(const fr_handle* h, int cut, int* th, int* tw, int* tc);
+int fr_features_at(fr_handle* h, const void* in, int in_fmt, int B, int H, int W, int cut, float* out, void* stream);
+
 /* Synchronize `stream`, then report (once) a split-stage wait that ran out in an FR_EMBED_ASYNC forward
  * of this handle since the last report: FR_ERR_STAGE, else FR_OK. */
 int fr_sync_check(fr_handle* h, void* stream);
@@ -620,6 +630,73 @@ int fr_head_backward(const float* X, int B, int K, int S, const float* W, int N,
                      const float* rstd2, const float* Z, const float* dY, float* dX /*NULL*/, float* dW /*NULL*/,
                      float* dbias /*NULL*/, float* dgamma1 /*NULL*/, float* dbeta1 /*NULL*/, float* dgamma2 /*NULL*/,
                      float* dbeta2 /*NULL*/, void* ws, size_t ws_bytes, void* stream);
+
+/* ---- Backbone training: convolution and BatchNorm2d in training mode, forward and backward, as ResNet-50's layer4
+ *      needs them (the reference's freeze_layers(model, 0.8), models/arcface/arcface_model.py:223, leaves exactly
+ *      backbone.layer4 trainable).  Handle-free, caller-owned f32 device buffers, each 16-byte aligned.
+ *      Layouts: activations physical NHWC, X [B][H][W][Cin], Z / dZ [B][OH][OW][Cout]; weights Wt / dW
+ *      [Cout][k][k][Cin] -- torch's channels_last memory of an NCHW-shaped activation and an OIHW-shaped weight.
+ *      k = 1 (pad 0) or 3 (pad 1), the same stride s in both directions, OH = (H + 2 pad - k) / s + 1 (OW likewise).
+ *      Convolution, with the optional input transform (scale / shift [Cin], both or neither; FR_CONV_IN_RELU only with
+ *      them), which is the folded BN (and ReLU) of the layer before and is applied while the operand is staged -- A is
+ *      never stored:
+ *        A[b,h,w,c] = X[b,h,w,c]                                  (no transform)
+ *                   = relu?(fma(X[b,h,w,c], scale[c], shift[c]))   (transform)
+ *        Z[b,oh,ow,n] = sum_{r,s,c} A[b, oh s + r - pad, ow s + s - pad, c] Wt[n,r,s,c], a tap outside the image
+ *        contributing +0: the padding is zero in A-space, not relu(shift).  Exact f32; the terms run in (r, s, c)
+ *        order, split-K partials merged in split order, the split a function of the shape alone.
+ *        dA[b,h,w,c] = sum_{r,s,n} dZ[b,oh,ow,n] Wt[n,r,s,c] over the taps with oh s + r - pad = h (likewise w) and
+ *        (oh, ow) inside the output; an input pixel no tap reaches gets +0.0f.  This is the gradient by A, not by X.
+ *        dW[n,r,s,c] = sum_{b,oh,ow} dZ[b,oh,ow,n] A[b, oh s + r - pad, ow s + s - pad, c]  (padded taps +0).
+ *        Every element of dA and dW has one owner and is written.
+ *      BatchNorm2d over Z viewed as [M][C], M = B OH OW (NHWC makes it a column statistic):
+ *        FR_BN_BATCH_STATS: mean_c = sum z / M, var_c = sum (z - mean_c)^2 / M (two passes, biased),
+ *        running_mean <- (1 - mom) running_mean + mom mean, running_var <- (1 - mom) running_var + mom var M / (M - 1);
+ *        else mean = running_mean, var = running_var and nothing is updated.
+ *        rstd = 1 / sqrt(var + eps) (IEEE), scale = gamma rstd, shift = beta - mean scale (each operation rounded).
+ *        y = fma(Z, scale, shift) (+ Res);  Y = relu?(y)   (FR_BN_RELU)
+ *        Backward from dY, z^ = (Z - mean) rstd:  dH = dY [y > 0] (dY without FR_BN_RELU; y is recomputed as above),
+ *        dRes = dH, dgamma = sum_m dH z^, dbeta = sum_m dH,
+ *        batch statistics: dZ = gamma rstd (dH - dbeta / M - z^ dgamma / M);  running statistics: dZ = dH scale.
+ *      One Bottleneck keeps only its raw conv outputs, its input and its output: relu(bn(Z1)) and relu(bn(Z2)) are the
+ *      transforms of conv2 and conv3 (forward and dW), and fr_bn_act_backward turns the dA of conv2 / conv3 into dZ1 /
+ *      dZ2 with Res = NULL.
+ *      Limits, each FR_ERR_ARG with a message before any HIP call: B, H, W >= 1, H, W <= 32768; Cin, Cout multiples of
+ *      4 in [4, 262144]; k in {1, 3}; stride in {1, 2}; B H W < 2^31; B H W Cin and B OH OW Cout <= 2^40
+ *      (all indexing is 64-bit); M in [1, 2^24], with FR_BN_BATCH_STATS M >= 2; C a multiple of 4 in [4, 2^24]; eps
+ *      finite and > 0; momentum in [0, 1]; no unknown flag bits; required pointers non-null; ws_bytes >=
+ *      fr_conv_train_workspace; at least one gradient requested.  Every result is bitwise repeatable and independent
+ *      of the workspace size: sums run in an order fixed by the shape, no floating-point atomics. ---- */
+#define FR_CONV_IN_RELU 1
+#define FR_BN_BATCH_STATS 1 /* = FR_HEAD_BATCH_STATS */
+#define FR_BN_RELU 2
+
+/* Bytes of device workspace fr_conv_train_forward needs (0 and a message on bad arguments): the split-K partials of Z
+ * when M is small, 16 otherwise.  The backward needs none. */
+size_t fr_conv_train_workspace(int B, int H, int W, int Cin, int Cout, int k, int stride);
+int fr_conv_train_forward(const float* X, int B, int H, int W, int Cin, const float* scale /*NULL*/,
+                          const float* shift /*NULL*/, int flags, const float* Wt, int Cout, int k, int stride, float* Z,
+                          void* ws, size_t ws_bytes, void* stream);
+/* Any of dA [B][H][W][Cin] and dW [Cout][k][k][Cin] (at least one non-NULL).  X, the transform and flags are the
+ * forward's.  With dA NULL (the conv sits on a frozen trunk) no B x H x W x Cin gradient is written anywhere. */
+int fr_conv_train_backward(const float* X, int B, int H, int W, int Cin, const float* scale /*NULL*/,
+                           const float* shift /*NULL*/, int flags, const float* Wt, int Cout, int k, int stride,
+                           const float* dZ, float* dA /*NULL*/, float* dW /*NULL*/, void* stream);
+/* mean, rstd, scale, shift [C] of one BatchNorm2d over Z [M][C]; flags: FR_BN_BATCH_STATS or 0.  running_* are read,
+ * and with FR_BN_BATCH_STATS written. */
+int fr_bn2d_train_stats(const float* Z, int64_t M, int C, const float* gamma, const float* beta, float* running_mean,
+                        float* running_var, int flags, float eps, float momentum, float* mean, float* rstd, float* scale,
+                        float* shift, void* stream);
+/* Y [M][C] = relu?(fma(Z, scale, shift) + Res?); flags: FR_BN_RELU or 0.  Needed only where the result must exist in
+ * memory: a block's output with its residual, and the downsample branch. */
+int fr_bn_act_forward(const float* Z, int64_t M, int C, const float* scale, const float* shift, const float* Res /*NULL*/,
+                      int flags, float* Y, void* stream);
+/* Any of dZ [M][C] (may be dY itself), dRes [M][C] (only with Res; not dY or dZ), dgamma, dbeta [C]; flags:
+ * FR_BN_BATCH_STATS | FR_BN_RELU as in the forward. */
+int fr_bn_act_backward(const float* dY, const float* Z, int64_t M, int C, const float* mean, const float* rstd,
+                       const float* gamma, const float* scale, const float* shift, const float* Res /*NULL*/, int flags,
+                       float* dZ /*NULL*/, float* dRes /*NULL*/, float* dgamma /*NULL*/, float* dbeta /*NULL*/,
+                       void* stream);
 
 /* ---- op-level entry points (kernel parity tests and custom graphs) ---- */
 
