@@ -27,7 +27,6 @@ namespace fr {
 namespace {
 
 constexpr int AUG_THREADS = 1024;
-constexpr int PB = 22;  // Pillow PRECISION_BITS
 
 struct AugParams {
     const uint8_t* in;
@@ -40,11 +39,6 @@ struct AugParams {
 };
 
 __device__ __forceinline__ int align16(int v) { return (v + 15) & ~15; }
-
-__device__ __forceinline__ uint8_t clip8(int v) {
-    v >>= PB;
-    return (uint8_t)(v < 0 ? 0 : (v > 255 ? 255 : v));
-}
 
 __device__ __forceinline__ int luma(int r, int g, int b) { return (19595 * r + 38470 * g + 7471 * b + 0x8000) >> 16; }
 

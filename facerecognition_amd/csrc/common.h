@@ -165,6 +165,62 @@ struct Num<true> {  // f16
     }
 };
 
+// ---- small reductions and orderings, each in one fixed order (what the bit-exact tests pin)
+
+// The sum over the wave's 64 lanes: a butterfly from 32 down to 1.  Every lane gets it.
+__device__ __forceinline__ float wave_sum(float v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
+    return v;
+}
+__device__ __forceinline__ double wave_sum(double v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
+    return v;
+}
+
+// The sum over a block of 256 threads: wave_sum's butterfly (written out: through the call hipcc schedules some
+// callers differently), then the four wave sums in wave order.  Every thread gets it.  red: 4 floats of LDS (reusable
+// at once: a barrier on both sides).
+__device__ __forceinline__ float block_sum_256(float v, float* red) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    __syncthreads();
+    if (lane == 0) red[wave] = v;
+    __syncthreads();
+    return red[0] + red[1] + red[2] + red[3];
+}
+
+// 256 threads as (g, cl) = (tid >> 4, tid & 15): the sum over the 16 row groups of column cl in group order; every
+// thread of the column gets it.  red: 16 x 17 floats.
+__device__ __forceinline__ float col_sum16(float v, float* red) {
+    const int cl = threadIdx.x & 15, g = threadIdx.x >> 4;
+    __syncthreads();
+    red[g * 17 + cl] = v;
+    __syncthreads();
+    float s = 0.f;
+#pragma unroll
+    for (int k = 0; k < 16; ++k) s += red[k * 17 + cl];
+    return s;
+}
+
+// A batch norm's normalised value, each operation rounded (never contracted into an fma)
+__device__ __forceinline__ float xhat(float x, float mean, float rstd) { return __fmul_rn(__fsub_rn(x, mean), rstd); }
+
+// The total order of the match results: score descending, index ascending.
+__device__ __forceinline__ bool better(float s1, int i1, float s2, int i2) {
+    return s1 > s2 || (s1 == s2 && i1 < i2);
+}
+
+// Pillow's fixed-point resampling: coefficients carry PB fraction bits, and an accumulated value becomes a pixel by
+// an arithmetic shift (floor, as Pillow's clip8 lookup) and a clamp to 0..255
+constexpr int PB = 22;  // Pillow PRECISION_BITS (32 - 8 - 2)
+__device__ __forceinline__ uint8_t clip8(int v) {
+    v >>= PB;
+    return (uint8_t)(v < 0 ? 0 : (v > 255 ? 255 : v));
+}
+
 // Border class of output pixel (oh, ow) for a bias9 table (3x3 / stride 1 / pad 1 with the input BN
 // folded into the weights): 3*rc + cc, rc = 0 top row, 1 interior, 2 bottom row (cc for columns).
 __device__ __forceinline__ int border_class(int oh, int ow, int Ho, int Wo) {

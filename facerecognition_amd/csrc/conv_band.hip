@@ -16,6 +16,7 @@
 // ReLU/PReLU, second affine output) stores 8-byte groups straight from registers.
 // LDS rows are 128 B (64 channels); chunk index XOR (row>>1)&7, applied to the per-lane DMA source.
 #include "kernels.h"
+#include "lds_dma.h"
 
 #include <hip/hip_ext.h>
 
@@ -23,34 +24,6 @@
 
 namespace fr {
 namespace {
-
-constexpr uint32_t OOB = 0x80000000u;
-typedef __attribute__((address_space(3))) void lds_void;
-
-__device__ __forceinline__ int swzb(int row, int chunk) { return chunk ^ ((row >> 1) & 7); }
-
-__device__ __forceinline__ void dma16(__amdgpu_buffer_rsrc_t rsrc, const char* lds, uint32_t voff) {
-    __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc, (lds_void*)lds, 16, voff, 0, 0, 0);
-}
-
-// ... with a wave-uniform byte offset in soffset (memory address only; the instruction's immediate
-// offset would also shift the LDS destination)
-__device__ __forceinline__ void dma16s(__amdgpu_buffer_rsrc_t rsrc, const char* lds, uint32_t voff, uint32_t soff) {
-    __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc, (lds_void*)lds, 16, voff, soff, 0, 0);
-}
-
-template <int N>
-__device__ __forceinline__ void wait_vm() {
-    if constexpr (N == 0) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    else if constexpr (N == 1) asm volatile("s_waitcnt vmcnt(1)" ::: "memory");
-    else if constexpr (N == 2) asm volatile("s_waitcnt vmcnt(2)" ::: "memory");
-    else if constexpr (N == 3) asm volatile("s_waitcnt vmcnt(3)" ::: "memory");
-    else if constexpr (N == 4) asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
-    else if constexpr (N == 5) asm volatile("s_waitcnt vmcnt(5)" ::: "memory");
-    else if constexpr (N == 6) asm volatile("s_waitcnt vmcnt(6)" ::: "memory");
-    else if constexpr (N == 7) asm volatile("s_waitcnt vmcnt(7)" ::: "memory");
-    else asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
-}
 
 constexpr int MAXPW = 8;  // max patch DMA instructions per wave per chunk
 
@@ -272,10 +245,10 @@ __global__ __launch_bounds__(64 * WM * WN, 1) void conv3x3_band_kernel(ConvArgs 
     const int band = rest % bands, b = rest / bands;
     const int oh0 = band * TH, n0 = tn * BN;
 
-    const uint32_t x_bytes = (uint32_t)min((size_t)0x7fffffff, (size_t)p.B * H * W * p.Cx * 2);
-    const __amdgpu_buffer_rsrc_t xr = __builtin_amdgcn_make_buffer_rsrc((void*)p.x, 0, x_bytes, 0x00020000);
-    const uint32_t w_bytes = (uint32_t)min((size_t)0x7fffffff, (size_t)p.Npad * p.Kpad * 2);
-    const __amdgpu_buffer_rsrc_t wr = __builtin_amdgcn_make_buffer_rsrc((void*)p.w, 0, w_bytes, 0x00020000);
+    const uint32_t x_bytes = clamp31((size_t)p.B * H * W * p.Cx * 2);
+    const __amdgpu_buffer_rsrc_t xr = buffer_rsrc(p.x, x_bytes);
+    const uint32_t w_bytes = clamp31((size_t)p.Npad * p.Kpad * 2);
+    const __amdgpu_buffer_rsrc_t wr = buffer_rsrc(p.w, w_bytes);
 
     // Patch DMA: instruction q -> chunk plane c = q / NPB, positions 64*(q % NPB) + lane.  The
     // source offsets are recomputed per chunk (Wp is a compile-time constant) to save registers.
@@ -306,7 +279,7 @@ __global__ __launch_bounds__(64 * WM * WN, 1) void conv3x3_band_kernel(ConvArgs 
 #pragma unroll
     for (int i = 0; i < FN; ++i) {
         const int row = wn * 16 * FN + 16 * i + (lane & 15);
-        boff[i] = row * 128 + swzb(row, lane >> 4) * 16;
+        boff[i] = row * 128 + swz(row, lane >> 4) * 16;
     }
 
     const int npw = __builtin_amdgcn_readfirstlane((PI - wave + NW - 1) / NW);  // this wave's patch instrs
@@ -408,11 +381,6 @@ __global__ __launch_bounds__(64 * WM * WN, 1) void conv3x3_band_kernel(ConvArgs 
     band_epilogue<T, W, Wp, Mv, FM, FN>(p, acc, lane, wm, wn, (size_t)(b * H + oh0) * W, n0);
 }
 
-template <int N>
-__device__ __forceinline__ void wait_vmn() {
-    asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
-}
-
 // Software-pipelined band kernel: one wave per SIMD (4 waves, 512-register budget), each wave owning
 // a 16*FM (pixel rows) x 16*FN (channels) register tile.  Per K-step s = (chunk, tap), K = 64 as two
 // MFMA k-halves:
@@ -458,10 +426,10 @@ __global__ __launch_bounds__(64 * WM * WN, 1) void conv3x3_bandp_kernel(ConvArgs
     const int band = rest % bands, b = rest / bands;
     const int oh0 = band * TH, n0 = tn * BN;
 
-    const uint32_t x_bytes = (uint32_t)min((size_t)0x7fffffff, (size_t)p.B * H * W * p.Cx * 2);
-    const __amdgpu_buffer_rsrc_t xr = __builtin_amdgcn_make_buffer_rsrc((void*)p.x, 0, x_bytes, 0x00020000);
-    const uint32_t w_bytes = (uint32_t)min((size_t)0x7fffffff, (size_t)p.Npad * p.Kpad * 2);
-    const __amdgpu_buffer_rsrc_t wr = __builtin_amdgcn_make_buffer_rsrc((void*)p.w, 0, w_bytes, 0x00020000);
+    const uint32_t x_bytes = clamp31((size_t)p.B * H * W * p.Cx * 2);
+    const __amdgpu_buffer_rsrc_t xr = buffer_rsrc(p.x, x_bytes);
+    const uint32_t w_bytes = clamp31((size_t)p.Npad * p.Kpad * 2);
+    const __amdgpu_buffer_rsrc_t wr = buffer_rsrc(p.w, w_bytes);
 
     // Patch DMA: wave w owns position blocks w*NBW .. w*NBW+NBW-1 (64 positions each) of all 8 channel
     // planes; a piece's plane only changes the source channel offset, carried in soffset.
@@ -489,7 +457,7 @@ __global__ __launch_bounds__(64 * WM * WN, 1) void conv3x3_bandp_kernel(ConvArgs
 #pragma unroll
     for (int i = 0; i < FN; ++i) {
         const int row = wn * 16 * FN + 16 * i + (lane & 15);
-        boff[i] = row * 128 + swzb(row, lane >> 4) * 16;
+        boff[i] = row * 128 + swz(row, lane >> 4) * 16;
         boff1[i] = boff[i] ^ 64;
     }
 
@@ -584,7 +552,7 @@ __global__ __launch_bounds__(64 * WM * WN, 1) void conv3x3_bandp_kernel(ConvArgs
                          : "=&v"(dummy) : "v"(base + o), "s"(wr) : "memory");
         }
     }
-    wait_vmn<0>();
+    wait_vm<0>();
     asm volatile("s_barrier" ::: "memory");
     pread(pA, 0, 0, 0);
 #pragma unroll
@@ -601,11 +569,11 @@ __global__ __launch_bounds__(64 * WM * WN, 1) void conv3x3_bandp_kernel(ConvArgs
         // Younger: slices step+2 .. step+WS-1 and the patch pieces issued in the last WS-1 steps
         // (at tap 0 of this chunk).
         if (WS == 3) {
-            if (tap == 0 || tap == 1) wait_vmn<(WS - 2) * NWI + NPW>();
-            else wait_vmn<(WS - 2) * NWI>();
+            if (tap == 0 || tap == 1) wait_vm<(WS - 2) * NWI + NPW>();
+            else wait_vm<(WS - 2) * NWI>();
         } else {
-            if (tap == 0) wait_vmn<NPW>();
-            else wait_vmn<0>();
+            if (tap == 0) wait_vm<NPW>();
+            else wait_vm<0>();
         }
         asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
         // k-half 1: prefetch k-half 0 of the next step; this step's slot (read-complete before the
@@ -635,7 +603,7 @@ __global__ __launch_bounds__(64 * WM * WN, 1) void conv3x3_bandp_kernel(ConvArgs
                 }
         }
     }
-    wait_vmn<0>();  // the tail re-fetches must land before the workgroup's LDS is released
+    wait_vm<0>();  // the tail re-fetches must land before the workgroup's LDS is released
 
     __syncthreads();  // every wave is past its last LDS read before the staging overwrites the ring
     band_epilogue_lds<T, W, Wp, Mv, FM, FN, WM, WN>(p, acc, smem, threadIdx.x, lane, wm, wn,

@@ -23,6 +23,7 @@
 // Bounds: per image 2 x 784 x 69,632 = 109 MFLOP against 802 KB of HBM traffic (x + y): at bs = 256
 // 206 MB per launch, the HBM stream, not the MFMA pipe (28 GFLOP), is the expected limit.
 #include "kernels.h"
+#include "lds_dma.h"
 
 #include <hip/hip_ext.h>
 
@@ -63,28 +64,6 @@ struct Geo {
     static_assert((8 * (IW * 16)) % 256 == 0 && TPL % 256 == 0 && (DS ? XPL % 256 == 0 : true), "conflict-free planes");
     static_assert(XROW % 1024 == 0 && LDS <= 160 * 1024, "DMA split / LDS");
 };
-
-typedef int v4i32 __attribute__((ext_vector_type(4)));
-#pragma clang diagnostic push
-#pragma clang diagnostic ignored "-Winline-asm"
-// 16-byte LDS-DMA (lane l lands at lds_addr + 16 l), invisible to the compiler's waitcnt pass (conv_trans.hip)
-__device__ __forceinline__ void dma16(const v4i32& rsrc, uint32_t lds_addr, uint32_t voff, uint32_t soff) {
-    asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tbuffer_load_dwordx4 %0, %1, %3 offen lds"
-                 :
-                 : "v"(voff), "s"(rsrc), "s"(__builtin_amdgcn_readfirstlane(lds_addr)), "s"(soff)
-                 : "memory", "m0");
-}
-#pragma clang diagnostic pop
-
-template <int N>
-__device__ __forceinline__ void wait_vm() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory"); }
-__device__ __forceinline__ void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
-
-template <bool F16>
-__device__ __forceinline__ uint2 pack4(float a, float b, float c, float d) {
-    if (F16) return make_uint2(pack2_f16(a, b), pack2_f16(c, d));
-    return make_uint2(pack2_bf16(a, b), pack2_bf16(c, d));
-}
 
 // Phase r waits for x row r + 2 (issued in phase r - 2, rows 0 / 1 before the loop).  VMEM ops per phase, in issue
 // order: D DMA instructions (the row r + 4; waves 0-5: two of the 14, 6-7: one), then S stores of row r - 2 when
@@ -137,8 +116,7 @@ __global__ __launch_bounds__(64 * NWV, 1) void bneck28_kernel(Chain17Args p) {
     // (piece = plane * 28 + pixel), wave w issues k = w and k = w + 8 (< 14); 64 channels -- k = 0..3, planes 2 k and
     // 2 k + 1 at 32 positions (positions 28-31 repeat pixel 27), waves 0-3 one each
     constexpr int CIN = G::CIN;
-    const uint64_t xp = (uint64_t)p.x;
-    const v4i32 xr = {(int)(uint32_t)xp, (int)((xp >> 32) & 0xffff), (int)((size_t)p.B * IW * IW * CIN * 2), 0x00020000};
+    const v4i32 xr = buffer_rsrc_words(p.x, (uint32_t)((size_t)p.B * IW * IW * CIN * 2));
     auto piece_src = [&](int k) {
         if (DS) {
             const int pl = 2 * k + (lane >> 5), x = min(lane & 31, IW - 1);
@@ -153,11 +131,11 @@ __global__ __launch_bounds__(64 * NWV, 1) void bneck28_kernel(Chain17Args p) {
         const uint32_t so = (uint32_t)(((size_t)b * IW + rr) * IW * CIN * 2);
         char* const dst = smem + X_OFF + (row % XR) * XROW;
         if (DS) {
-            if (wave < 4) dma16(xr, (uint32_t)(uintptr_t)(dst + 1024 * wave), src0, so);
+            if (wave < 4) dma16_asm(xr, (uint32_t)(uintptr_t)(dst + 1024 * wave), src0, so);
             return;
         }
-        dma16(xr, (uint32_t)(uintptr_t)(dst + 1024 * wave), src0, so);
-        if (wave + 8 < 14) dma16(xr, (uint32_t)(uintptr_t)(dst + 1024 * (wave + 8)), src1, so);
+        dma16_asm(xr, (uint32_t)(uintptr_t)(dst + 1024 * wave), src0, so);
+        if (wave + 8 < 14) dma16_asm(xr, (uint32_t)(uintptr_t)(dst + 1024 * (wave + 8)), src1, so);
     };
     dma_row(0);
     dma_row(1);

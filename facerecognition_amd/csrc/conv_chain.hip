@@ -28,6 +28,7 @@
 // CU streams every weight byte: 64 FLOP per weight byte at M = 64, so the L2 -> CU weight stream, not the MFMA
 // pipe, is the expected limit); HBM: x read once and y written once per image (115 KB each).
 #include "kernels.h"
+#include "lds_dma.h"
 
 #include <hip/hip_ext.h>
 
@@ -57,35 +58,9 @@ constexpr int RING = 14;                           // register ring (fragments);
 constexpr int BIAS_BLK = 4 * 128 + CX;            // 1408 floats per block: A | B | C | D (128 each) | E (896)
 static_assert(KSA % RING == 0 && (KSE * NFE) % RING == 0 && FRAGS % RING == 0, "ring slots must be compile-time");
 
-typedef int v4i32 __attribute__((ext_vector_type(4)));
-#pragma clang diagnostic push
-#pragma clang diagnostic ignored "-Winline-asm"
-// 16-byte LDS-DMA (lane l lands at lds_addr + 16 l), invisible to the compiler's waitcnt pass (conv_trans.hip)
-__device__ __forceinline__ void dma16(const v4i32& rsrc, uint32_t lds_addr, uint32_t voff, uint32_t soff) {
-    asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tbuffer_load_dwordx4 %0, %1, %3 offen lds"
-                 :
-                 : "v"(voff), "s"(rsrc), "s"(__builtin_amdgcn_readfirstlane(lds_addr)), "s"(soff)
-                 : "memory", "m0");
-}
-#pragma clang diagnostic pop
-
-// The lane id recomputed where used (v_mbcnt in volatile asm, never hoisted or kept live across the block loop):
-// the loop-invariant per-lane addresses of all five passes would otherwise stay live for the whole kernel and
-// push the E pass into scratch spills, whose reloads wait for the entire weight ring (conv_stage.hip fresh_lane)
-__device__ __forceinline__ int fresh_lane() {
-    int l;
-    asm volatile("v_mbcnt_lo_u32_b32 %0, -1, 0\n\tv_mbcnt_hi_u32_b32 %0, -1, %0" : "=v"(l));
-    return l;
-}
-
-__device__ __forceinline__ void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
-
-template <bool F16>
-__device__ __forceinline__ uint2 pack4(float a, float b, float c, float d) {
-    if (F16) return make_uint2(pack2_f16(a, b), pack2_f16(c, d));
-    return make_uint2(pack2_bf16(a, b), pack2_bf16(c, d));
-}
-
+// The lane id is fresh_lane() wherever it is used: the loop-invariant per-lane addresses of all five passes would
+// otherwise stay live for the whole kernel and push the E pass into scratch spills, whose reloads wait for the
+// entire weight ring
 template <bool F16>
 __global__ __launch_bounds__(64 * NWV, 1) void chain17_kernel(Chain17Args p) {
     typedef Num<F16> T;
@@ -96,16 +71,15 @@ __global__ __launch_bounds__(64 * NWV, 1) void chain17_kernel(Chain17Args p) {
     if (b >= p.B) return;
 
     // ---- bias tables: block `blk` into slot `slot` (waves 0-1: the A-D part, 2-5: the E part)
-    const uint64_t bp = (uint64_t)p.bias;
-    const v4i32 br = {(int)(uint32_t)bp, (int)((bp >> 32) & 0xffff), (int)(p.nblk * BIAS_BLK * 4), 0x00020000};
+    const v4i32 br = buffer_rsrc_words(p.bias, (uint32_t)(p.nblk * BIAS_BLK * 4));
     auto issue_bias = [&](int blk, int slot) {
         const uint32_t so = (uint32_t)(blk * BIAS_BLK * 4);
         const int lane = fresh_lane();
         if (wave < 2) {
-            dma16(br, (uint32_t)(uintptr_t)(smem + pb_off(slot) + wave * 1024), (uint32_t)(wave * 1024 + lane * 16), so);
+            dma16_asm(br, (uint32_t)(uintptr_t)(smem + pb_off(slot) + wave * 1024), (uint32_t)(wave * 1024 + lane * 16), so);
         } else if (wave < 5 || (wave == 5 && lane < 32)) {
             const int q = wave - 2;  // 1-KiB piece of the E part
-            dma16(br, (uint32_t)(uintptr_t)(smem + qb_off(slot) + q * 1024), (uint32_t)(2048 + q * 1024 + lane * 16), so);
+            dma16_asm(br, (uint32_t)(uintptr_t)(smem + qb_off(slot) + q * 1024), (uint32_t)(2048 + q * 1024 + lane * 16), so);
         }
     };
 
@@ -122,7 +96,7 @@ __global__ __launch_bounds__(64 * NWV, 1) void chain17_kernel(Chain17Args p) {
 
     // ---- the wave's weight stream
     const uint32_t w_bytes = (uint32_t)((size_t)NWV * p.nblk * FRAGS * 1024);
-    const __amdgpu_buffer_rsrc_t wr = __builtin_amdgcn_make_buffer_rsrc((void*)p.w, 0, w_bytes, 0x00020000);
+    const __amdgpu_buffer_rsrc_t wr = buffer_rsrc(p.w, w_bytes);
     frag wq[RING];
     auto wload = [&](int slot, int g) {  // fragment g of this wave's stream (past the end: zeros, never used)
         wq[slot] = __builtin_bit_cast(frag, __builtin_amdgcn_raw_buffer_load_b128(wr, (uint32_t)(fresh_lane() * 16), (uint32_t)g * 1024u, 0));

@@ -23,6 +23,7 @@
 // Bounds: per image and block 2 x 289 x (256 x 96 + 3 x 288 x 32 + 96 x 256) = 44.4 MFLOP; global traffic per image
 // and block: x read twice (staging, residual) and y written once (148 KB each), L2 / Infinity-Cache served.
 #include "kernels.h"
+#include "lds_dma.h"
 
 #include <hip/hip_ext.h>
 
@@ -51,18 +52,6 @@ constexpr int W21_O = W1_E, W22_O = W21_O + W2_E, W3_O = W22_O + W2_E, W4_O = W3
 constexpr int WBLK = W4_O + W4_E;          // 76,800 elements per block
 // per-block biases: 96 | 32 | 32 | 32 | 256
 constexpr int BB2A = 96, BB2B = 128, BB3 = 160, BB4 = 192, BBLK = 448;
-
-__device__ __forceinline__ int fresh_lane() {
-    int l;
-    asm volatile("v_mbcnt_lo_u32_b32 %0, -1, 0\n\tv_mbcnt_hi_u32_b32 %0, -1, %0" : "=v"(l));
-    return l;
-}
-
-template <bool F16>
-__device__ __forceinline__ uint2 pack4(float a, float b, float c, float d) {
-    if (F16) return make_uint2(pack2_f16(a, b), pack2_f16(c, d));
-    return make_uint2(pack2_bf16(a, b), pack2_bf16(c, d));
-}
 
 // padded position of pixel p (the discarded pixels >= 289 take pixel 0's: their taps stay inside the plane)
 __device__ __forceinline__ int ppos(int p) {

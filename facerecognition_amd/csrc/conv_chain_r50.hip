@@ -24,6 +24,7 @@
 // against 2.23 MB of weights: the L2 -> CU weight stream (571 MB per block at bs = 256), not the MFMA pipe, is the
 // expected limit; HBM: x read once and y written once per image (100 KB each).
 #include "kernels.h"
+#include "lds_dma.h"
 
 #include <hip/hip_ext.h>
 
@@ -56,33 +57,6 @@ constexpr int FRAGS = KS1 * NF12 + KS2 * NF12 + 2 * KS3 * NF3;   // 272 weight f
 constexpr int RING = 16;                                          // register ring (fragments)
 static_assert((KS1 * NF12) % RING == 0 && (KS2 * NF12) % RING == 0 && (KS3 * NF3) % RING == 0, "compile-time ring slots");
 
-typedef int v4i32 __attribute__((ext_vector_type(4)));
-#pragma clang diagnostic push
-#pragma clang diagnostic ignored "-Winline-asm"
-// 16-byte LDS-DMA (lane l lands at lds_addr + 16 l), invisible to the compiler's waitcnt pass (conv_trans.hip)
-__device__ __forceinline__ void dma16(const v4i32& rsrc, uint32_t lds_addr, uint32_t voff, uint32_t soff) {
-    asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tbuffer_load_dwordx4 %0, %1, %3 offen lds"
-                 :
-                 : "v"(voff), "s"(rsrc), "s"(__builtin_amdgcn_readfirstlane(lds_addr)), "s"(soff)
-                 : "memory", "m0");
-}
-#pragma clang diagnostic pop
-
-// the lane id recomputed where used (never hoisted or kept live across the block loop: conv_chain.hip)
-__device__ __forceinline__ int fresh_lane() {
-    int l;
-    asm volatile("v_mbcnt_lo_u32_b32 %0, -1, 0\n\tv_mbcnt_hi_u32_b32 %0, -1, %0" : "=v"(l));
-    return l;
-}
-
-__device__ __forceinline__ void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
-
-template <bool F16>
-__device__ __forceinline__ uint2 pack4(float a, float b, float c, float d) {
-    if (F16) return make_uint2(pack2_f16(a, b), pack2_f16(c, d));
-    return make_uint2(pack2_bf16(a, b), pack2_bf16(c, d));
-}
-
 template <bool F16>
 __global__ __launch_bounds__(64 * NWV, 1) void chain_r50_kernel(Chain17Args p) {
     typedef Num<F16> T;
@@ -93,11 +67,10 @@ __global__ __launch_bounds__(64 * NWV, 1) void chain_r50_kernel(Chain17Args p) {
     if (b >= p.B) return;
 
     // ---- bias tables: block `blk` into slot `slot` (waves 0-5, one 1-KiB piece each)
-    const uint64_t bp = (uint64_t)p.bias;
-    const v4i32 br = {(int)(uint32_t)bp, (int)((bp >> 32) & 0xffff), (int)(p.nblk * BIAS_B), 0x00020000};
+    const v4i32 br = buffer_rsrc_words(p.bias, (uint32_t)(p.nblk * BIAS_B));
     auto issue_bias = [&](int blk, int slot) {
         if (wave < BIAS_B / 1024)
-            dma16(br, (uint32_t)(uintptr_t)(smem + BIAS_OFF + slot * BIAS_B + wave * 1024),
+            dma16_asm(br, (uint32_t)(uintptr_t)(smem + BIAS_OFF + slot * BIAS_B + wave * 1024),
                   (uint32_t)(wave * 1024 + fresh_lane() * 16), (uint32_t)(blk * BIAS_B));
     };
 
@@ -114,7 +87,7 @@ __global__ __launch_bounds__(64 * NWV, 1) void chain_r50_kernel(Chain17Args p) {
 
     // ---- the wave's weight stream
     const uint32_t w_bytes = (uint32_t)((size_t)NWV * p.nblk * FRAGS * 1024);
-    const __amdgpu_buffer_rsrc_t wr = __builtin_amdgcn_make_buffer_rsrc((void*)p.w, 0, w_bytes, 0x00020000);
+    const __amdgpu_buffer_rsrc_t wr = buffer_rsrc(p.w, w_bytes);
     frag wq[RING];
     auto wload = [&](int slot, int g) {  // fragment g of this wave's stream (past the end: zeros, never used)
         wq[slot] = __builtin_bit_cast(frag, __builtin_amdgcn_raw_buffer_load_b128(wr, (uint32_t)(fresh_lane() * 16), (uint32_t)g * 1024u, 0));

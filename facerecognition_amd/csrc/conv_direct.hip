@@ -21,6 +21,7 @@
 //     activation, as conv_igemm's epilogue8) are the implicit GEMM's, so the output equals conv_igemm
 //     tile 0 bit for bit and the per-shape autotuner can time this kernel beside the igemm tiles.
 #include "kernels.h"
+#include "lds_dma.h"
 
 #include <hip/hip_ext.h>
 
@@ -30,9 +31,6 @@ namespace {
 constexpr int DNW = 4;    // waves, one per SIMD
 constexpr int KSR1 = 12;  // register-resident K-steps at one workgroup per CU: Kpad <= 384
 constexpr int KSR2 = 10;  // ... at two (NF = 2 only): Kpad <= 320
-constexpr uint32_t OOB = 0x80000000u;
-
-typedef __attribute__((address_space(3))) void lds_void;
 
 struct DGeo {
     int PST;      // bytes per patch position (CINB, + 32 when CINB / 16 is even)
@@ -67,8 +65,7 @@ __global__ __launch_bounds__(64 * DNW, OCC) void conv_direct_kernel(ConvArgs p, 
     const int n0 = ng * 16 * NF;
 
     // ---- weights -> VGPRs (K-steps past Kpad / 32 are zero and never used)
-    const __amdgpu_buffer_rsrc_t wr = __builtin_amdgcn_make_buffer_rsrc(
-        (void*)p.w, 0, (uint32_t)min((size_t)0x7fffffff, (size_t)p.Npad * p.Kpad * 2), 0x00020000);
+    const __amdgpu_buffer_rsrc_t wr = buffer_rsrc(p.w, clamp31((size_t)p.Npad * p.Kpad * 2));
     frag wa[KSR][NF];
 #pragma unroll
     for (int ks = 0; ks < KSR; ++ks)
@@ -101,10 +98,10 @@ __global__ __launch_bounds__(64 * DNW, OCC) void conv_direct_kernel(ConvArgs p, 
         }
     }
 
-    const uint32_t x_bytes = (uint32_t)min((size_t)0x7fffffff, (size_t)p.B * H * W * p.Cx * 2);
-    const __amdgpu_buffer_rsrc_t xr = __builtin_amdgcn_make_buffer_rsrc((void*)p.x, 0, x_bytes, 0x00020000);
-    const uint32_t y_bytes = (uint32_t)min((size_t)0x7fffffff, (size_t)p.M * p.Cy * 2);
-    const __amdgpu_buffer_rsrc_t yr = __builtin_amdgcn_make_buffer_rsrc((void*)p.y, 0, y_bytes, 0x00020000);
+    const uint32_t x_bytes = clamp31((size_t)p.B * H * W * p.Cx * 2);
+    const __amdgpu_buffer_rsrc_t xr = buffer_rsrc(p.x, x_bytes);
+    const uint32_t y_bytes = clamp31((size_t)p.M * p.Cy * 2);
+    const __amdgpu_buffer_rsrc_t yr = buffer_rsrc(p.y, y_bytes);
 
     struct Unit {
         int b, p0, p1, oh0, ih0, rows;
@@ -236,8 +233,7 @@ __global__ __launch_bounds__(64 * DNW, 1) void conv_direct1_kernel(ConvArgs p, D
     if (k0 >= g.units) return;
     const int n0 = ng * 16 * NF, M = p.M;
 
-    const __amdgpu_buffer_rsrc_t wr = __builtin_amdgcn_make_buffer_rsrc(
-        (void*)p.w, 0, (uint32_t)min((size_t)0x7fffffff, (size_t)p.Npad * p.Kpad * 2), 0x00020000);
+    const __amdgpu_buffer_rsrc_t wr = buffer_rsrc(p.w, clamp31((size_t)p.Npad * p.Kpad * 2));
     frag wa[KSR][NF];
 #pragma unroll
     for (int ks = 0; ks < KSR; ++ks)
@@ -253,12 +249,9 @@ __global__ __launch_bounds__(64 * DNW, 1) void conv_direct1_kernel(ConvArgs p, D
         bias4[i] = p.bias ? *(const float4*)(p.bias + n) : make_float4(0.f, 0.f, 0.f, 0.f);
         slope4[i] = p.act == 2 ? *(const float4*)(p.slope + n) : make_float4(0.f, 0.f, 0.f, 0.f);
     }
-    const __amdgpu_buffer_rsrc_t xr = __builtin_amdgcn_make_buffer_rsrc(
-        (void*)p.x, 0, (uint32_t)min((size_t)0x7fffffff, (size_t)M * p.Cx * 2), 0x00020000);
-    const __amdgpu_buffer_rsrc_t yr = __builtin_amdgcn_make_buffer_rsrc(
-        (void*)p.y, 0, (uint32_t)min((size_t)0x7fffffff, (size_t)M * p.Cy * 2), 0x00020000);
-    const __amdgpu_buffer_rsrc_t rr = __builtin_amdgcn_make_buffer_rsrc(
-        (void*)(p.res ? p.res : p.y), 0, (uint32_t)(p.res ? min((size_t)0x7fffffff, (size_t)M * p.Cres * 2) : 0), 0x00020000);
+    const __amdgpu_buffer_rsrc_t xr = buffer_rsrc(p.x, clamp31((size_t)M * p.Cx * 2));
+    const __amdgpu_buffer_rsrc_t yr = buffer_rsrc(p.y, clamp31((size_t)M * p.Cy * 2));
+    const __amdgpu_buffer_rsrc_t rr = buffer_rsrc(p.res ? p.res : p.y, p.res ? clamp31((size_t)M * p.Cres * 2) : 0);
     typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
 
     auto load_unit = [&](int k, frag (&fb)[KSR][FW], u32x2 (&rs)[NF][FW]) {

@@ -12,6 +12,7 @@
 // The epilogue optionally records amax(|y|) of what it stores (atomicMax on the f32 bit pattern) for
 // the next conv.  Requirements: Cin % 64 == 0 (every IResNet100 conv but the bf16 stem).
 #include "kernels.h"
+#include "lds_dma.h"
 
 #include <hip/hip_ext.h>
 
@@ -19,17 +20,9 @@ namespace fr {
 namespace {
 
 constexpr int KS = 128;                // K per step
-constexpr uint32_t OOB = 0x80000000u;
-typedef __attribute__((address_space(3))) void lds_void;
 typedef __attribute__((ext_vector_type(8))) int i32x8_t;
 typedef __attribute__((ext_vector_type(2))) __bf16 bf16x2_t;
 typedef __attribute__((ext_vector_type(2))) short i16x2_t;
-
-__device__ __forceinline__ int swz(int row, int chunk) { return chunk ^ ((row >> 1) & 7); }
-
-__device__ __forceinline__ void dma16(__amdgpu_buffer_rsrc_t rsrc, const char* lds, uint32_t voff) {
-    __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc, (lds_void*)lds, 16, voff, 0, 0, 0);
-}
 
 // power-of-two activation scale exponent: amax / 2^e <= 448
 __device__ __forceinline__ int act_exp(const float* amax, int slots) {
@@ -86,10 +79,10 @@ __global__ __launch_bounds__(64 * WM * WN, (Fp8Occ<BM, BN>::value)) void conv_fp
 
     const int lrow = lane >> 3;
     const int cl = (lane & 7) ^ ((4 * wave + (lane >> 4)) & 7);
-    const uint32_t x_bytes = (uint32_t)min((size_t)0x7fffffff, (size_t)p.B * p.H * p.W * p.Cx * 2);
-    const __amdgpu_buffer_rsrc_t xr = __builtin_amdgcn_make_buffer_rsrc((void*)p.x, 0, x_bytes, 0x00020000);
-    const uint32_t w_bytes = (uint32_t)min((size_t)0x7fffffff, (size_t)p.Npad * p.Kpad);
-    const __amdgpu_buffer_rsrc_t wr = __builtin_amdgcn_make_buffer_rsrc((void*)p.w8, 0, w_bytes, 0x00020000);
+    const uint32_t x_bytes = clamp31((size_t)p.B * p.H * p.W * p.Cx * 2);
+    const __amdgpu_buffer_rsrc_t xr = buffer_rsrc(p.x, x_bytes);
+    const uint32_t w_bytes = clamp31((size_t)p.Npad * p.Kpad);
+    const __amdgpu_buffer_rsrc_t wr = buffer_rsrc(p.w8, w_bytes);
 
     const int HoWo = p.Ho * p.Wo;
     int a_ih[NA], a_iw[NA];

@@ -19,6 +19,7 @@
 // makes the MFMA-fragment ds_read_b128 loads bank-conflict free.
 // FASTK (Cin % 64 == 0): a K-step is one (r, s) tap and 64 channels, tracked in scalars.
 #include "kernels.h"
+#include "lds_dma.h"
 
 #include <hip/hip_ext.h>
 
@@ -31,20 +32,6 @@ typedef unsigned int v4u32_t __attribute__((ext_vector_type(4)));
 namespace {
 
 constexpr int BK = 64;
-constexpr uint32_t OOB = 0x80000000u;  // buffer offset past num_records → the DMA writes zeros
-
-__device__ __forceinline__ int swz(int row, int chunk) { return chunk ^ ((row >> 1) & 7); }
-
-template <int N>
-__device__ __forceinline__ void wait_vmn() {
-    asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
-}
-
-typedef __attribute__((address_space(3))) void lds_void;
-
-__device__ __forceinline__ void dma16(__amdgpu_buffer_rsrc_t rsrc, const char* lds, uint32_t voff) {
-    __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc, (lds_void*)lds, 16, voff, 0, 0, 0);
-}
 
 // Shared fused epilogue for 8 consecutive channels n..n+7 of output pixel m.
 template <bool F16>
@@ -130,10 +117,10 @@ void conv_igemm_kernel(ConvArgs p, int tiles_n, int kt_per_split) {
     const int lrow = lane >> 3;
     const int cl = (lane & 7) ^ ((4 * wave + (lane >> 4)) & 7);
 
-    const uint32_t x_bytes = (uint32_t)min((size_t)0x7fffffff, (size_t)p.B * p.H * p.W * p.Cx * 2);
-    const __amdgpu_buffer_rsrc_t xr = __builtin_amdgcn_make_buffer_rsrc((void*)p.x, 0, x_bytes, 0x00020000);
-    const uint32_t w_bytes = (uint32_t)min((size_t)0x7fffffff, (size_t)p.Npad * p.Kpad * 2);
-    const __amdgpu_buffer_rsrc_t wr = __builtin_amdgcn_make_buffer_rsrc((void*)p.w, 0, w_bytes, 0x00020000);
+    const uint32_t x_bytes = clamp31((size_t)p.B * p.H * p.W * p.Cx * 2);
+    const __amdgpu_buffer_rsrc_t xr = buffer_rsrc(p.x, x_bytes);
+    const uint32_t w_bytes = clamp31((size_t)p.Npad * p.Kpad * 2);
+    const __amdgpu_buffer_rsrc_t wr = buffer_rsrc(p.w, w_bytes);
 
     const int HoWo = p.Ho * p.Wo;
     int a_ih[NA], a_iw[NA];
@@ -162,9 +149,8 @@ void conv_igemm_kernel(ConvArgs p, int tiles_n, int kt_per_split) {
     }
     // K-steps from kt_x2 on read x2 (the K-concatenated 1x1 projection)
     const int kt_x2 = FASTK && p.x2 ? p.K1 / BK : nkt;
-    const __amdgpu_buffer_rsrc_t x2r = __builtin_amdgcn_make_buffer_rsrc(
-        (void*)(p.x2 ? p.x2 : p.x), 0,
-        (uint32_t)min((size_t)0x7fffffff, p.x2 ? (size_t)p.B * p.H2 * p.W2 * p.Cx2 * 2 : (size_t)0), 0x00020000);
+    const __amdgpu_buffer_rsrc_t x2r =
+        buffer_rsrc(p.x2 ? p.x2 : p.x, clamp31(p.x2 ? (size_t)p.B * p.H2 * p.W2 * p.Cx2 * 2 : (size_t)0));
     uint32_t b_base[NB];
 #pragma unroll
     for (int j = 0; j < NB; ++j) b_base[j] = (uint32_t)(((n0 + 8 * (wave + NW * j) + lrow) * p.Kpad + 8 * cl) * 2);
@@ -319,7 +305,7 @@ void conv_igemm_kernel(ConvArgs p, int tiles_n, int kt_per_split) {
             compute(buf);
             // next stage landed (this wave's DMA; the younger residual loads may stay in flight), then
             // every wave's; raw barrier: __syncthreads() would also drain the residual loads
-            if (pre_res && kt >= kres) wait_vmn<ITER>();
+            if (pre_res && kt >= kres) wait_vm<ITER>();
             else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
             asm volatile("s_barrier" ::: "memory");
             buf ^= 1;
@@ -369,8 +355,7 @@ void conv_igemm_kernel(ConvArgs p, int tiles_n, int kt_per_split) {
     if (p.partial) {
         // in-launch reduction: the partial slabs go through sc1 (write-through, coherent across XCDs) buffer stores
         // and loads (cdna_hip_programming.md §6 Guideline 16 R1), besides the release / acquire pair below
-        const __amdgpu_buffer_rsrc_t pr = __builtin_amdgcn_make_buffer_rsrc(
-            (void*)p.partial, 0, (uint32_t)min((size_t)0x7fffffff, (size_t)gridDim.y * p.M * p.Npad * 4), 0x00020000);
+        const __amdgpu_buffer_rsrc_t pr = buffer_rsrc(p.partial, clamp31((size_t)gridDim.y * p.M * p.Npad * 4));
 #pragma unroll
         for (int it = 0; it < ITER; ++it) {
             const int ml = ml0 + it * RS, m = m0 + ml;
@@ -391,18 +376,18 @@ void conv_igemm_kernel(ConvArgs p, int tiles_n, int kt_per_split) {
         // publishes its partial tile (agent-scope release before the ticket); the slice that draws the last
         // ticket acquires, sums the tile's partials in split order and runs the split-K epilogue's arithmetic
         // (splitk_epilogue_kernel: the same bits), one kernel boundary per split conv fewer.
-        wait_vmn<0>();
+        wait_vm<0>();
         __syncthreads();  // every wave's partial stores issued and waited; sE no longer read
         volatile int* flag = (volatile int*)smem;
         if (tid == 0) {
             __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
-            wait_vmn<0>();
+            wait_vm<0>();
             const int t = __hip_atomic_fetch_add(p.splitk_cnt + lid, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             const int last = t == (int)gridDim.y - 1;
             if (last) {
                 __hip_atomic_store(p.splitk_cnt + lid, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
                 __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-                wait_vmn<0>();
+                wait_vm<0>();
             }
             *flag = last;
         }

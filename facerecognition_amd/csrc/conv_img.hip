@@ -17,6 +17,7 @@
 //   * operand A = weight rows, operand B = patch positions, so a lane ends with 4 consecutive channels
 //     of one pixel; the epilogue (bias or border-class bias9, residual, ReLU/PReLU) stores 8 B per lane.
 #include "kernels.h"
+#include "lds_dma.h"
 
 #include <hip/hip_ext.h>
 
@@ -51,14 +52,6 @@ struct ImgGeo {
 typedef ImgGeo<28, 128, 7, 32, 2> Geo28;  // layer2: 2 x 2 waves of 7 frags x 64 channels, 64 KiB LDS
 typedef ImgGeo<56, 64, 4, 64, 4> Geo56;   // layer1: 4 waves of 4 frags (one virtual row) x 64 channels
 
-constexpr uint32_t OOB = 0x80000000u;
-typedef __attribute__((address_space(3))) void lds_void;
-
-// LDS-DMA of 16 B per lane; soff: a wave-uniform byte offset (memory address only)
-__device__ __forceinline__ void dma16s(__amdgpu_buffer_rsrc_t rsrc, const char* lds, uint32_t voff, uint32_t soff) {
-    __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc, (lds_void*)lds, 16, voff, soff, 0, 0);
-}
-
 // mid-step wait: vmcnt(N); LDS ops older than the step's L youngest (its next-step patch reads, which
 // no DMA of this step touches) complete -- the weight refills of the slot about to be overwritten and
 // the staged patch writes that the next barrier publishes
@@ -83,10 +76,9 @@ __global__ __launch_bounds__(256, 2) void conv_img_kernel(ConvArgs p) {
     const int wm = wave % G::PG, wn = wave / G::PG;  // pixel frags FM*wm.., output channels 16*FN*wn..
     const int b = blockIdx.x / G::BANDS, r0 = G::QR * (blockIdx.x % G::BANDS);
 
-    const uint32_t x_bytes = (uint32_t)min((size_t)0x7fffffff, (size_t)p.B * IW * IW * p.Cx * 2);
-    const __amdgpu_buffer_rsrc_t xr = __builtin_amdgcn_make_buffer_rsrc((void*)p.x, 0, x_bytes, 0x00020000);
-    const __amdgpu_buffer_rsrc_t wr =
-        __builtin_amdgcn_make_buffer_rsrc((void*)p.wimg, 0, (uint32_t)(NSTEP * SLICE_B), 0x00020000);
+    const uint32_t x_bytes = clamp31((size_t)p.B * IW * IW * p.Cx * 2);
+    const __amdgpu_buffer_rsrc_t xr = buffer_rsrc(p.x, x_bytes);
+    const __amdgpu_buffer_rsrc_t wr = buffer_rsrc(p.wimg, (uint32_t)(NSTEP * SLICE_B));
 
     // patch of chunk cc (input channels 32cc..): PP pieces per wave, plane-major [4 planes][QR+2 rows]
     // [PC positions][16 B]; halo, pad and spare pieces read out of range (zeros).  Offsets recomputed

@@ -25,6 +25,7 @@
 //   * built with -mllvm -amdgpu-mfma-vgpr-form (Makefile): the 56 accumulators live in VGPRs, so the
 //     epilogue and the seeding need no AGPR <-> VGPR moves (280 per unit otherwise).
 #include "kernels.h"
+#include "lds_dma.h"
 
 #include <hip/hip_ext.h>
 
@@ -44,13 +45,6 @@ constexpr int WSLICE_B = 4 * 64 * 16;                          // 4096: one K-st
 constexpr int NKS = 18;                                        // K-steps (2 channel groups x 9 taps)
 constexpr int W_B = NKS * WSLICE_B;                            // 73728
 constexpr int ROWS_LDS = W_B + 2 * PATCH_B;                    // 163840 = all of the CU's LDS
-constexpr uint32_t OOB = 0x80000000u;
-
-typedef __attribute__((address_space(3))) void lds_void;
-
-__device__ __forceinline__ void dma16(__amdgpu_buffer_rsrc_t rsrc, const char* lds, uint32_t voff) {
-    __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc, (lds_void*)lds, 16, voff, 0, 0, 0);
-}
 
 struct Unit {
     int b, r0, c0;
@@ -80,10 +74,9 @@ __global__ __launch_bounds__(256, 1) void conv_rows_kernel(ConvArgs p, int NG, i
     const int ng = blockIdx.x % NG, k0 = blockIdx.x / NG, kstride = gridDim.x / NG;
     if (k0 >= units) return;
 
-    const uint32_t x_bytes = (uint32_t)min((size_t)0x7fffffff, (size_t)p.B * H * W * p.Cx * 2);
-    const __amdgpu_buffer_rsrc_t xr = __builtin_amdgcn_make_buffer_rsrc((void*)p.x, 0, x_bytes, 0x00020000);
-    const __amdgpu_buffer_rsrc_t wr =
-        __builtin_amdgcn_make_buffer_rsrc((void*)(p.wimg + (size_t)ng * (W_B / 2)), 0, (uint32_t)W_B, 0x00020000);
+    const uint32_t x_bytes = clamp31((size_t)p.B * H * W * p.Cx * 2);
+    const __amdgpu_buffer_rsrc_t xr = buffer_rsrc(p.x, x_bytes);
+    const __amdgpu_buffer_rsrc_t wr = buffer_rsrc(p.wimg + (size_t)ng * (W_B / 2), (uint32_t)W_B);
 
     // ---- DMA of a unit's patch into buffer `buf`: slot q = (row, pos, chunk'), logical 8-channel
     // group = chunk' ^ (pos & 7) (the swizzle lives in the source offset; the DMA destination is linear)
@@ -286,10 +279,9 @@ __global__ __launch_bounds__(512, 1) void conv_rows_pp_kernel(ConvArgs p, int NG
     const int ng = blockIdx.x % NG, k0 = blockIdx.x / NG, kstride = gridDim.x / NG;
     if (k0 >= units) return;
 
-    const uint32_t x_bytes = (uint32_t)min((size_t)0x7fffffff, (size_t)p.B * H * W * p.Cx * 2);
-    const __amdgpu_buffer_rsrc_t xr = __builtin_amdgcn_make_buffer_rsrc((void*)p.x, 0, x_bytes, 0x00020000);
-    const __amdgpu_buffer_rsrc_t wr =
-        __builtin_amdgcn_make_buffer_rsrc((void*)(p.wimg + (size_t)ng * (W_B / 2)), 0, (uint32_t)W_B, 0x00020000);
+    const uint32_t x_bytes = clamp31((size_t)p.B * H * W * p.Cx * 2);
+    const __amdgpu_buffer_rsrc_t xr = buffer_rsrc(p.x, x_bytes);
+    const __amdgpu_buffer_rsrc_t wr = buffer_rsrc(p.wimg + (size_t)ng * (W_B / 2), (uint32_t)W_B);
     const int pbase = W_B + grp * PATCH_B;  // this group's patch buffer (LDS byte offset)
     typedef __attribute__((address_space(3))) int lds_int;
     lds_int* const gctr = (lds_int*)(uintptr_t)(pbase + PSLOTS * 16);

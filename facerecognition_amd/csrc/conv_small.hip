@@ -21,13 +21,12 @@
 // NF = 2 / 1 (one wave per 16 px x 32 / 16 ch) is also a candidate at large M: the N = 32 / 96 convs of FaceNet's
 // Block35 at bs = 256 fill half of an implicit-GEMM tile's 64 or 128 columns.
 #include "kernels.h"
+#include "lds_dma.h"
 
 #include <hip/hip_ext.h>
 
 namespace fr {
 namespace {
-
-constexpr uint32_t OOB = 0x80000000u;
 
 template <bool F16, int KS, int NFR>
 __global__ __launch_bounds__(KS == 1 ? 256 : 64 * KS) void conv_small_kernel(ConvArgs p, int n_mf, int n_units) {
@@ -46,13 +45,10 @@ __global__ __launch_bounds__(KS == 1 ? 256 : 64 * KS) void conv_small_kernel(Con
     const int mb = mv ? m / HoWo : 0, mr = mv ? m - mb * HoWo : 0, oh = mr / p.Wo, ow = mr - oh * p.Wo;
     const int ih0 = oh * p.sh - p.ph, iw0 = ow * p.sw - p.pw;
 
-    const __amdgpu_buffer_rsrc_t xr = __builtin_amdgcn_make_buffer_rsrc(
-        (void*)p.x, 0, (uint32_t)min((size_t)0x7fffffff, (size_t)p.B * p.H * p.W * p.Cx * 2), 0x00020000);
-    const __amdgpu_buffer_rsrc_t x2r = __builtin_amdgcn_make_buffer_rsrc(
-        (void*)(p.x2 ? p.x2 : p.x), 0,
-        (uint32_t)min((size_t)0x7fffffff, p.x2 ? (size_t)p.B * p.H2 * p.W2 * p.Cx2 * 2 : (size_t)0), 0x00020000);
-    const __amdgpu_buffer_rsrc_t wr = __builtin_amdgcn_make_buffer_rsrc(
-        (void*)p.w, 0, (uint32_t)min((size_t)0x7fffffff, (size_t)p.Npad * p.Kpad * 2), 0x00020000);
+    const __amdgpu_buffer_rsrc_t xr = buffer_rsrc(p.x, clamp31((size_t)p.B * p.H * p.W * p.Cx * 2));
+    const __amdgpu_buffer_rsrc_t x2r =
+        buffer_rsrc(p.x2 ? p.x2 : p.x, clamp31(p.x2 ? (size_t)p.B * p.H2 * p.W2 * p.Cx2 * 2 : (size_t)0));
+    const __amdgpu_buffer_rsrc_t wr = buffer_rsrc(p.w, clamp31((size_t)p.Npad * p.Kpad * 2));
     const int K1 = p.x2 ? p.K1 : p.K;          // the conv's own K; the projection K-steps follow
     const int nks_all = p.Kpad / 32;
     // this wave's K chunk [s_beg, s_end) (all of K for KS = 1)

@@ -38,6 +38,7 @@
 // most 8 (PARTS - 1) ids behind it, so the neighbours of every resident workgroup are resident or next in
 // line whatever the grid size (layer2 at B = 256: 512 workgroups on 256 CUs = two full rounds).
 #include "kernels.h"
+#include "lds_dma.h"
 
 #include <hip/hip_ext.h>
 
@@ -84,24 +85,8 @@ typedef SplitGeo<56, 64, 4, 64> Split56;   // layer1: 8 pixel groups x 1 channel
 
 constexpr int NW = 8;                     // waves
 constexpr int FN = 4;                     // channel fragments per wave
-constexpr uint32_t OOB = 0x80000000u;
 constexpr int SPIN_LIMIT = 1 << 21;       // default: x s_sleep 1 (64 cycles): ~0.1 s, then the wait has run out
 constexpr int SC1 = 16;                   // buffer-load cache policy: sc1 (L1 bypass; gfx940+ cpol bit 4)
-
-
-typedef __attribute__((address_space(3))) void lds_void;
-
-// threadIdx.x through an empty asm: loop-invariant copy-out addresses are recomputed where they are used
-// instead of being hoisted to the kernel's start and spilled across the K loops
-__device__ __forceinline__ int opaque_tid() {
-    int t = threadIdx.x;
-    asm volatile("" : "+v"(t));
-    return t;
-}
-
-__device__ __forceinline__ void dma16s(__amdgpu_buffer_rsrc_t rsrc, const char* lds, uint32_t voff, uint32_t soff) {
-    __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc, (lds_void*)lds, 16, voff, soff, 0, 0);
-}
 
 // K-step order within a pair of 32-channel groups (18 positions): the 3 dh = 1 taps of both groups first
 // (they read own rows only), then dh = 0 and dh = 2 (which also read the halo rows).  The halo rows of a
@@ -137,14 +122,12 @@ __global__ __launch_bounds__(64 * NW, 1) void split_stage_kernel(StageArgs p) {
     const int nconv_all = nconv + (G::TAIL ? p.ntail : 0);
     const int total = nconv_all * KSTEPS;
 
-    const __amdgpu_buffer_rsrc_t wr =
-        __builtin_amdgcn_make_buffer_rsrc((void*)p.w, 0, (uint32_t)min((size_t)0x7fffffff, (size_t)total * SLICE_B), 0x00020000);
+    const __amdgpu_buffer_rsrc_t wr = buffer_rsrc(p.w, clamp31((size_t)total * SLICE_B));
 
     // ---- initial patch: image rows r0-1 .. r0+14 (out-of-image rows and halo columns read as zeros)
     {
         // (the resources span this image only: 32-bit offsets at any batch size)
-        const __amdgpu_buffer_rsrc_t xr = __builtin_amdgcn_make_buffer_rsrc(
-            (void*)(p.x + (size_t)b * IW * IW * C), 0, IW * IW * C * 2, 0x00020000);
+        const __amdgpu_buffer_rsrc_t xr = buffer_rsrc(p.x + (size_t)b * IW * IW * C, IW * IW * C * 2);
         for (int u = 0; u < PATCH_B / 1024 / NW; ++u) {
             const int piece = wave + NW * u, q = piece * 64 + lane;
             const int plane = q / PPOS, pos = q % PPOS, ir = r0 - 1 + pos / PC, ic = pos % PC - 1;
@@ -212,10 +195,8 @@ __global__ __launch_bounds__(64 * NW, 1) void split_stage_kernel(StageArgs p) {
     // for the others), so a slot holds those 6 rows.  Slot 1 is DMA'd at conv1's start, slot 0 (the next
     // block's) at conv2's start; the K loop's per-step vmcnt waits and barriers complete them.
     const int tbase = part == 0 ? 0 : 1;
-    const __amdgpu_buffer_rsrc_t epr =
-        __builtin_amdgcn_make_buffer_rsrc((void*)p.ep, 0, (uint32_t)((size_t)nconv_all * 9 * C * 4), 0x00020000);
-    const __amdgpu_buffer_rsrc_t slr =
-        __builtin_amdgcn_make_buffer_rsrc((void*)p.slope, 0, (uint32_t)((size_t)nconv_all * C * 4), 0x00020000);
+    const __amdgpu_buffer_rsrc_t epr = buffer_rsrc(p.ep, (uint32_t)((size_t)nconv_all * 9 * C * 4));
+    const __amdgpu_buffer_rsrc_t slr = buffer_rsrc(p.slope, (uint32_t)((size_t)nconv_all * C * 4));
     auto issue_tab = [&](int cv, int cv_slope, int slot) {
         char* dst = smem + G::TAB + slot * G::TS;
         int lane = opaque_tid() & 63;  // opaque: the DMA offsets are not hoisted out of the block loop
@@ -264,8 +245,8 @@ __global__ __launch_bounds__(64 * NW, 1) void split_stage_kernel(StageArgs p) {
     // every launch of this stage), so no memset has to precede the launch.  A neighbour's counter
     // reaching f0 + cv + 1 means its conv cv rows are published.
     const int f0 = __hip_atomic_load(my_flag, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    const __amdgpu_buffer_rsrc_t xr_x = __builtin_amdgcn_make_buffer_rsrc(
-        (void*)(p.xchg + (size_t)b * PARTS * 2 * 2 * XROW), 0, PARTS * 2 * 2 * XROW * 2, 0x00020000);
+    const __amdgpu_buffer_rsrc_t xr_x =
+        buffer_rsrc(p.xchg + (size_t)b * PARTS * 2 * 2 * XROW, PARTS * 2 * 2 * XROW * 2);
     // element offset (within this image's exchange rows) of row `which` of part `pt`, parity `par`
     auto xrow_off = [&](int pt, int which, int par) { return ((pt * 2 + which) * 2 + par) * XROW; };
 

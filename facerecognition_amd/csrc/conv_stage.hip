@@ -26,6 +26,7 @@
 //     per K-step, two waves per SIMD (the second hides the first's LDS and L2 waits); operand A =
 //     weight rows, operand B = patch positions, so a lane ends with 4 consecutive channels of one pixel.
 #include "kernels.h"
+#include "lds_dma.h"
 
 #include <hip/hip_ext.h>
 
@@ -48,7 +49,6 @@ constexpr int TS = TAB_ROWS_B + SC * 4;      // + the PReLU slopes of the conv b
 constexpr int TAB = PATCH_B + PAD_B;
 constexpr int STAGE_LDS = TAB + 2 * TS;      // 134400
 constexpr int KSTEPS = (SC / 32) * 9;        // 72 per conv
-constexpr uint32_t OOB = 0x80000000u;
 constexpr int SNW = 8;                       // waves per workgroup: 2 pixel halves x 4 channel groups
 constexpr int FN = 4;                        // 16-channel fragments per wave
 constexpr int NPW = 16 * FN;                 // output channels per wave
@@ -57,20 +57,6 @@ constexpr int NPW = 16 * FN;                 // output channels per wave
 // wait ~30 % of each conv at the epilogue barrier for the 6-fragment ones, take 2 and fit 256 VGPRs without
 // epilogue spills; the 6-fragment waves 3; the one-wave-per-SIMD variant 6
 constexpr int RING7 = 2, RING6 = 3, RING13 = 6;
-
-typedef __attribute__((address_space(3))) void lds_void;
-
-// The lane id / thread id recomputed where used (v_mbcnt; volatile, so never hoisted, CSE'd or kept
-// live across the conv loop): a long-lived copy of threadIdx.x gets spilled, and each scratch reload
-// waits for every outstanding VMEM load (vmcnt(0)), i.e. drains the weight prefetch ring.
-__device__ __forceinline__ int fresh_lane() {
-    int l;
-    asm volatile("v_mbcnt_lo_u32_b32 %0, -1, 0\n\tv_mbcnt_hi_u32_b32 %0, -1, %0" : "=v"(l));
-    return l;
-}
-__device__ __forceinline__ int opaque_tid() {
-    return (__builtin_amdgcn_readfirstlane(threadIdx.x) & ~63) + fresh_lane();
-}
 
 template <bool F16>
 __global__ __launch_bounds__(64 * SNW, 1) void stage_kernel(StageArgs p) {
@@ -85,14 +71,13 @@ __global__ __launch_bounds__(64 * SNW, 1) void stage_kernel(StageArgs p) {
     const int nconv = 2 * p.nblk;
     const int total = nconv * KSTEPS;
 
-    const uint32_t w_bytes = (uint32_t)min((size_t)0x7fffffff, (size_t)total * SLICE_B);
-    const __amdgpu_buffer_rsrc_t wr = __builtin_amdgcn_make_buffer_rsrc((void*)p.w, 0, w_bytes, 0x00020000);
+    const uint32_t w_bytes = clamp31((size_t)total * SLICE_B);
+    const __amdgpu_buffer_rsrc_t wr = buffer_rsrc(p.w, w_bytes);
 
     // ---- initial patch: x of this image; the patch is 7168 16-B slots (plane-major), 112 pieces of 64
     {
         // (the resource spans this image only: 32-bit offsets at any batch size)
-        const __amdgpu_buffer_rsrc_t xr =
-            __builtin_amdgcn_make_buffer_rsrc((void*)(p.x + (size_t)b * SPIX * SC), 0, SPIX * SC * 2, 0x00020000);
+        const __amdgpu_buffer_rsrc_t xr = buffer_rsrc(p.x + (size_t)b * SPIX * SC, SPIX * SC * 2);
         for (int u = 0; u < PATCH_B / 1024 / SNW; ++u) {
             const int piece = wave + SNW * u, q = piece * 64 + lane;
             const int plane = q / PPOS, pos = q - plane * PPOS, r = pos / SWP, c = pos % SWP - 1;
@@ -155,13 +140,11 @@ __global__ __launch_bounds__(64 * SNW, 1) void stage_kernel(StageArgs p) {
     // both land long before use (loads retire in order; the weight loads behind them are waited on).
     // A lane's 4 channels n..n+3 of fragment i and its column class are fixed, and its output row is
     // interior except for fragment j = 0 of wave row 0 (image row 0) and j = 6 of wave row 1 (row 13).
-    const __amdgpu_buffer_rsrc_t epr =
-        __builtin_amdgcn_make_buffer_rsrc((void*)p.ep, 0, (uint32_t)((size_t)nconv * TAB_ROWS_B), 0x00020000);
-    const __amdgpu_buffer_rsrc_t slr =
-        __builtin_amdgcn_make_buffer_rsrc((void*)p.slope, 0, (uint32_t)((size_t)nconv * SC * 4), 0x00020000);
+    const __amdgpu_buffer_rsrc_t epr = buffer_rsrc(p.ep, (uint32_t)((size_t)nconv * TAB_ROWS_B));
+    const __amdgpu_buffer_rsrc_t slr = buffer_rsrc(p.slope, (uint32_t)((size_t)nconv * SC * 4));
     auto issue_tab = [&](int cv, int cv_slope, int slot) {
         char* dst = smem + TAB + slot * TS;
-        int lane = opaque_tid() & 63;  // opaque: the DMA offsets are not hoisted out of the block loop
+        int lane = fresh_tid() & 63;  // opaque: the DMA offsets are not hoisted out of the block loop
 #pragma unroll
         for (int u = 0; u < (TAB_ROWS_B / 1024 + SNW - 1) / SNW; ++u) {
             const int piece = wave + SNW * u;
@@ -286,13 +269,13 @@ __global__ __launch_bounds__(64 * SNW, 1) void stage_kernel(StageArgs p) {
         if (p.dbg_x) dbg = second ? p.dbg_x[cv >> 1] : p.dbg_t[cv >> 1];
         bf16_t* const yo = second && cv == nconv - 1 ? p.y : dbg;
         if (yo) {  // NHWC copies from the patch (the stage output once; intermediates every conv)
-            for (int c = opaque_tid(); c < SPIX * (SC / 8); c += 64 * SNW) {
+            for (int c = fresh_tid(); c < SPIX * (SC / 8); c += 64 * SNW) {
                 const int pix = c / (SC / 8), pl = c - pix * (SC / 8), r = pix / SW, col = pix - r * SW;
                 const uint4 v = *(const uint4*)(smem + pl * PLANE_B + (r * SWP + col + 1) * 16);
                 *(uint4*)(yo + img + (size_t)pix * SC + pl * 8) = v;
             }
             if (dbg && yo != dbg) {
-                for (int c = opaque_tid(); c < SPIX * (SC / 8); c += 64 * SNW) {
+                for (int c = fresh_tid(); c < SPIX * (SC / 8); c += 64 * SNW) {
                     const int pix = c / (SC / 8), pl = c - pix * (SC / 8), r = pix / SW, col = pix - r * SW;
                     const uint4 v = *(const uint4*)(smem + pl * PLANE_B + (r * SWP + col + 1) * 16);
                     *(uint4*)(dbg + img + (size_t)pix * SC + pl * 8) = v;
@@ -444,14 +427,13 @@ __device__ __forceinline__ void stage13_body(const StageArgs& p, char* smem, con
     const int nconv = 2 * p.nblk;               // the blocks' convs; then p.ntail tail halves (run_tail)
     const int nconv_all = nconv + p.ntail;
     const int total = nconv_all * KSTEPS;
-    const uint32_t w_bytes = (uint32_t)min((size_t)0x7fffffff, (size_t)total * SLICE_B);
-    const __amdgpu_buffer_rsrc_t wr = __builtin_amdgcn_make_buffer_rsrc((void*)p.w, 0, w_bytes, 0x00020000);
+    const uint32_t w_bytes = clamp31((size_t)total * SLICE_B);
+    const __amdgpu_buffer_rsrc_t wr = buffer_rsrc(p.w, w_bytes);
 
     // ---- initial patch (halo rows and columns read as zeros): 128 pieces of 1 KiB
     {
         // (the resource spans this image only: 32-bit offsets at any batch size)
-        const __amdgpu_buffer_rsrc_t xr =
-            __builtin_amdgcn_make_buffer_rsrc((void*)(p.x + (size_t)b * SPIX * SC), 0, SPIX * SC * 2, 0x00020000);
+        const __amdgpu_buffer_rsrc_t xr = buffer_rsrc(p.x + (size_t)b * SPIX * SC, SPIX * SC * 2);
         for (int u = 0; u < (PATCH13_B / 1024 + NWV - 1) / NWV; ++u) {
             const int piece = wave + NWV * u, q = piece * 64 + lane;
             if (piece >= PATCH13_B / 1024) break;
@@ -508,10 +490,8 @@ __device__ __forceinline__ void stage13_body(const StageArgs& p, char* smem, con
     };
 
     const size_t img = (size_t)b * SPIX * SC;
-    const __amdgpu_buffer_rsrc_t epr =
-        __builtin_amdgcn_make_buffer_rsrc((void*)p.ep, 0, (uint32_t)((size_t)nconv_all * TAB_ROWS_B), 0x00020000);
-    const __amdgpu_buffer_rsrc_t slr =
-        __builtin_amdgcn_make_buffer_rsrc((void*)p.slope, 0, (uint32_t)((size_t)nconv_all * SC * 4), 0x00020000);
+    const __amdgpu_buffer_rsrc_t epr = buffer_rsrc(p.ep, (uint32_t)((size_t)nconv_all * TAB_ROWS_B));
+    const __amdgpu_buffer_rsrc_t slr = buffer_rsrc(p.slope, (uint32_t)((size_t)nconv_all * SC * 4));
     auto issue_tab = [&](int cv, int cv_slope, int slot) {
         char* dst = smem + TAB13 + slot * TS13;
         int ln = fresh_lane();
@@ -621,13 +601,13 @@ __device__ __forceinline__ void stage13_body(const StageArgs& p, char* smem, con
         if (p.dbg_x) dbg = second ? p.dbg_x[cv >> 1] : p.dbg_t[cv >> 1];
         bf16_t* const yo = second && cv == nconv - 1 ? p.y : dbg;
         if (yo) {
-            for (int c = opaque_tid(); c < SPIX * (SC / 8); c += 64 * NWV) {
+            for (int c = fresh_tid(); c < SPIX * (SC / 8); c += 64 * NWV) {
                 const int pix = c / (SC / 8), pl = c - pix * (SC / 8);
                 const uint4 v = *(const uint4*)(smem + pl * PLANE13_B + pix_pos13(pix / SW, pix % SW) * 16);
                 *(uint4*)(yo + img + (size_t)pix * SC + pl * 8) = v;
             }
             if (dbg && yo != dbg) {
-                for (int c = opaque_tid(); c < SPIX * (SC / 8); c += 64 * NWV) {
+                for (int c = fresh_tid(); c < SPIX * (SC / 8); c += 64 * NWV) {
                     const int pix = c / (SC / 8), pl = c - pix * (SC / 8);
                     const uint4 v = *(const uint4*)(smem + pl * PLANE13_B + pix_pos13(pix / SW, pix % SW) * 16);
                     *(uint4*)(dbg + img + (size_t)pix * SC + pl * 8) = v;

@@ -18,6 +18,7 @@
 // a block output is rounded to bf16 first (the residual stream), and the next conv1 quantizes that value,
 // as the per-conv path (conv_fp8.hip reading the bf16 tensor) does.
 #include "kernels.h"
+#include "lds_dma.h"
 
 #include <hip/hip_ext.h>
 
@@ -38,14 +39,7 @@ constexpr int KST = 2 * 9;                      // K-steps per conv: 2 halves of
 constexpr int WSTEP_B = 4 * SC * 32;            // 32768: [4 groups][256 rows][32 B]
 constexpr int NW = 8, FN = 4, FM = 7, NPW = 64;
 
-typedef __attribute__((address_space(3))) void lds_void;
 typedef __attribute__((ext_vector_type(8))) int i32x8_t;
-
-__device__ __forceinline__ int opaque_tid() {
-    int t = threadIdx.x;
-    asm volatile("" : "+v"(t));
-    return t;
-}
 
 // smallest e with amax / 2^e <= 448 (0 for an all-zero input), clamped to the e8m0 range we use
 __device__ __forceinline__ int act_exp(float a) {
@@ -90,14 +84,12 @@ __global__ __launch_bounds__(64 * NW, 1) void stage8_kernel(StageArgs p) {
     const int nconv = 2 * p.nblk;
     const int total = nconv * KST;
     const uint8_t* w8 = (const uint8_t*)p.w;
-    const __amdgpu_buffer_rsrc_t wr = __builtin_amdgcn_make_buffer_rsrc(
-        (void*)w8, 0, (uint32_t)min((size_t)0x7fffffff, (size_t)total * WSTEP_B), 0x00020000);
+    const __amdgpu_buffer_rsrc_t wr = buffer_rsrc(w8, clamp31((size_t)total * WSTEP_B));
     const size_t img = (size_t)b * SPIX * SC;
 
     // ---- X <- the stage input (bf16 NHWC): 6272 16-B slots, plane-major; Q <- zeros (the halo)
     {
-        const __amdgpu_buffer_rsrc_t xr = __builtin_amdgcn_make_buffer_rsrc(
-            (void*)p.x, 0, (uint32_t)min((size_t)0x7fffffff, (size_t)p.B * SPIX * SC * 2), 0x00020000);
+        const __amdgpu_buffer_rsrc_t xr = buffer_rsrc(p.x, clamp31((size_t)p.B * SPIX * SC * 2));
         for (int u = 0; u < (X_B / 1024 + NW - 1) / NW; ++u) {
             const int piece = wave + NW * u;
             if (piece < X_B / 1024) {

@@ -18,6 +18,7 @@
 //   * 3 K-steps of v_mfma_f32_16x16x32_{bf16,f16} per tile; the epilogue (bias, PReLU) stages the
 //     224 x 64 tile in LDS (16-B chunks XOR-swizzled by pixel) and writes it with 16-B coalesced stores.
 #include "kernels.h"
+#include "lds_dma.h"
 
 #include <hip/hip_ext.h>
 
@@ -33,7 +34,7 @@ constexpr int SROWS = 2;      // output rows per tile
 constexpr int SPIX = SROWS * SW;  // 224
 constexpr int WROW = 104;          // LDS weight row: 96 bf16 + pad (208 B: conflict-free 16-lane reads)
 
-// Workgroup barrier that waits for LDS only: __syncthreads()'s fence also drains vmcnt, i.e. every 16-B
+// The tile loop's barriers are lds_barrier(): __syncthreads()'s fence also drains vmcnt, i.e. every 16-B
 // output store of the previous tile (gfx950 counts stores in vmcnt) and the next tile's prefetched input
 // rows, so each tile's 28 KiB of stores would run exposed instead of behind the next tile's work.
 constexpr int OFF_SY = 0;                                     // 28672
@@ -48,7 +49,6 @@ static_assert(OFF_SX % 16 == 0 && OFF_SBS % 16 == 0 && OFF_RAW % 16 == 0, "16-B 
 // compiler then does not know about the LDS write, and its waitcnt pass does not guard every later LDS
 // access with a vmcnt(0) (which would also drain the output stores); the kernel's own waits cover the DMA
 // (m0 is reserved to the compiler, hence the pragma; nothing else in this kernel uses m0)
-typedef int v4i32 __attribute__((ext_vector_type(4)));
 #pragma clang diagnostic push
 #pragma clang diagnostic ignored "-Winline-asm"
 __device__ __forceinline__ void dma_dword(const v4i32& rsrc, uint32_t lds_addr, uint32_t voff) {
@@ -58,8 +58,6 @@ __device__ __forceinline__ void dma_dword(const v4i32& rsrc, uint32_t lds_addr, 
                  : "memory", "m0");
 }
 #pragma clang diagnostic pop
-
-__device__ __forceinline__ void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
 
 template <bool F16>
 // waves_per_eu(3): the persistent loop would otherwise grow past 168 VGPRs and lose the third block per CU
@@ -103,16 +101,14 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) void s
     // sraw buffer), two tiles ahead (one DMA latency per tile, under write load, was most of a tile's
     // time), branch free: rows outside the image, the pad dwords and tiles past the end get an
     // out-of-range offset, which reads 0.  The waits are explicit (see the loop top).
-    const uint64_t inp = (uint64_t)in;
-    const v4i32 inr = {(int)(uint32_t)inp, (int)((inp >> 32) & 0xffff), (int)((ntiles / (SW / SROWS)) * (SW * SW * 3)),
-                       0x00020000};
+    const v4i32 inr = buffer_rsrc_words(in, (uint32_t)((ntiles / (SW / SROWS)) * (SW * SW * 3)));
     auto dma_raw = [&](int t, int buf) {
         const int b = t / (SW / SROWS), r0 = (t % (SW / SROWS)) * SROWS;
 #pragma unroll
         for (int j = 0; j < 2; ++j) {
             const int e = tid + 256 * j, rr = e / (SW * 3 / 4), d = e % (SW * 3 / 4), ir = r0 - 1 + rr;
             const bool ok = e < RAWD && (unsigned)ir < (unsigned)SW;
-            const uint32_t off = ok ? (uint32_t)(((b * SW + ir) * SW * 3) + 4 * d) : 0x80000000u;
+            const uint32_t off = ok ? (uint32_t)(((b * SW + ir) * SW * 3) + 4 * d) : OOB;
             dma_dword(inr, (uint32_t)(uintptr_t)&sraw[512 * buf + 256 * j + 64 * wave], off);
         }
     };

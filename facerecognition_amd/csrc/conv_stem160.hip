@@ -29,6 +29,7 @@
 // 1a as stored, 72); HBM: the u8 crop once (76.8 KB; the prepared input, 409.6 KB, for f32 input) + the conv2d_3b
 // output once (231 KB).
 #include "kernels.h"
+#include "lds_dma.h"
 
 #include <hip/hip_ext.h>
 
@@ -52,34 +53,9 @@ constexpr int STEM_END = PO_OFF + 2 * PO_ROW;         // 153088
 constexpr int STEM_LDS = STEM_END + 2048;             // discarded columns' taps read up to 2 positions past a row
 constexpr int NPH = 44;                               // phases: maxpool row s - 5, 3b row s - 6 (s = 6 .. 43)
 constexpr int C3B = 80;                               // conv2d_3b output channels
-constexpr uint32_t OOB = 0x80000000u;
 static_assert(STEM_LDS <= 163840, "lds");
 
-typedef int v4i32 __attribute__((ext_vector_type(4)));
-#pragma clang diagnostic push
-#pragma clang diagnostic ignored "-Winline-asm"
-// 16-byte LDS-DMA (lane l lands at lds_addr + 16 l), invisible to the compiler's waitcnt pass (conv_trans.hip):
-// the phase-end vmcnt(0) covers it
-__device__ __forceinline__ void dma16(const v4i32& rsrc, uint32_t lds_addr, uint32_t voff) {
-    asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tbuffer_load_dwordx4 %0, %1, 0 offen lds"
-                 :
-                 : "v"(voff), "s"(rsrc), "s"(__builtin_amdgcn_readfirstlane(lds_addr))
-                 : "memory", "m0");
-}
-#pragma clang diagnostic pop
-
-template <bool F16>
-__device__ __forceinline__ uint2 pack4(float a, float b, float c, float d) {
-    if (F16) return make_uint2(pack2_f16(a, b), pack2_f16(c, d));
-    return make_uint2(pack2_bf16(a, b), pack2_bf16(c, d));
-}
-
-__device__ __forceinline__ int fresh_lane() {
-    int l;
-    asm volatile("v_mbcnt_lo_u32_b32 %0, -1, 0\n\tv_mbcnt_hi_u32_b32 %0, -1, %0" : "=v"(l));
-    return l;
-}
-
+// The input rows move by dma16_asm: the phase-end vmcnt(0) covers them
 template <bool F16, bool U8>
 __global__ __launch_bounds__(256, 1) void stem160_kernel(Stem160Args p) {
     typedef Num<F16> T;
@@ -122,15 +98,14 @@ __global__ __launch_bounds__(256, 1) void stem160_kernel(Stem160Args p) {
     // ---- input rows: DMA of row `row` (3 pieces: slots 0-63, 64-127, 128-159) into its ring slot; out of the
     // image: zeros (OOB offsets)
     const uint32_t in_bytes = (uint32_t)(IW * IW * 16);
-    const uint64_t xp = (uint64_t)(p.x + (size_t)b * IW * IW * 8);
-    const v4i32 xr = {(int)(uint32_t)xp, (int)((xp >> 32) & 0xffff), (int)in_bytes, 0x00020000};
+    const v4i32 xr = buffer_rsrc_words(p.x + (size_t)b * IW * IW * 8, in_bytes);
     auto dma_piece = [&](int row, int piece) {  // piece 0..2 of the row
         const int ln = fresh_lane();
         const int q = 64 * piece + ln;  // de-interleaved slot
         if (q < IW) {
             const int pos = q < 80 ? 2 * q : 2 * (q - 80) + 1;
             const uint32_t off = row < IW ? (uint32_t)((row * IW + pos) * 16) : OOB;
-            dma16(xr, (uint32_t)(uintptr_t)(smem + IN_OFF + (row % IN_SLOTS) * IN_ROW + piece * 1024), off);
+            dma16_asm(xr, (uint32_t)(uintptr_t)(smem + IN_OFF + (row % IN_SLOTS) * IN_ROW + piece * 1024), off);
         }
     };
     // u8 crops: thread t < 40 k converts positions 4 (t % 40) .. + 3 of row (first + t / 40) into the prepared

@@ -18,6 +18,7 @@
 // summation order of the conv differs.  Bounds: 2 x 3136 x 64 x 392 = 157 MFLOP (of which 52 / 49 padding) per
 // image, 200 KB in, 100 KB out: at bs = 256 40 GFLOP and 77 MB of HBM.
 #include "kernels.h"
+#include "lds_dma.h"
 
 #include <hip/hip_ext.h>
 
@@ -40,22 +41,6 @@ constexpr int RAWB = 2048;                   // (two waves' DMA spans)
 constexpr int SR50_LDS = RAW_OFF + 2 * RAWB; // 88064
 constexpr int KS = 13;                       // K-steps: 52 tap slots of 8 channels (49 used)
 constexpr int NWV = 8;
-
-typedef int v4i32 __attribute__((ext_vector_type(4)));
-#pragma clang diagnostic push
-#pragma clang diagnostic ignored "-Winline-asm"
-// 16-byte LDS-DMA (lane l lands at lds_addr + 16 l), invisible to the compiler's waitcnt pass (conv_trans.hip)
-__device__ __forceinline__ void dma16(const v4i32& rsrc, uint32_t lds_addr, uint32_t voff) {
-    asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tbuffer_load_dwordx4 %0, %1, 0 offen lds"
-                 :
-                 : "v"(voff), "s"(rsrc), "s"(__builtin_amdgcn_readfirstlane(lds_addr))
-                 : "memory", "m0");
-}
-#pragma clang diagnostic pop
-
-template <int N>
-__device__ __forceinline__ void wait_vm() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory"); }
-__device__ __forceinline__ void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
 
 // Phase m waits for input group G(m) = rows 4m + 2 .. 4m + 5 (issued in phase m - 2; G(-2) .. G(1) before the
 // loop).  VMEM ops per phase: one DMA instruction (G(m + 2)), then, for m >= 1, S pooled-row stores (waves 0-3: one,
@@ -108,25 +93,23 @@ __global__ __launch_bounds__(64 * NWV, 1) void stem_r50_kernel(StemR50Args p) {
 
     // ---- input DMA: group G(k) = rows 4k + 2 .. 4k + 5; wave w moves row 4k + 2 + (w >> 1), parity plane w & 1: lane
     // i = padded column 2i + (w & 1), pixel 2i + (w & 1) - 3 (outside the row or the image: offset out of range, 0)
-    const uint64_t xp = (uint64_t)p.x;
-    const v4i32 xr = {(int)(uint32_t)xp, (int)((xp >> 32) & 0xffff), (int)((size_t)p.B * IH * IH * 16), 0x00020000};
+    const v4i32 xr = buffer_rsrc_words(p.x, (uint32_t)((size_t)p.B * IH * IH * 16));
     const int dpx = 2 * lane + (wave & 1) - 3;
     auto dma_group = [&](int k) {
         const int row = 4 * k + 2 + (wave >> 1);
         const bool ok = (unsigned)row < (unsigned)IH && (unsigned)dpx < (unsigned)IH;
-        const uint32_t off = ok ? (uint32_t)((((size_t)b * IH + row) * IH + dpx) * 16) : 0x80000000u;
-        dma16(xr, (uint32_t)(uintptr_t)(smem + X_OFF + ((row + 8) % XR) * XROWB + (wave & 1) * XPAR), off);
+        const uint32_t off = ok ? (uint32_t)((((size_t)b * IH + row) * IH + dpx) * 16) : OOB;
+        dma16_asm(xr, (uint32_t)(uintptr_t)(smem + X_OFF + ((row + 8) % XR) * XROWB + (wave & 1) * XPAR), off);
     };
     // ---- u8 crops (U8): group G(k) = 1344 contiguous bytes (21 16-B chunks per row) into raw slot k & 1 by waves 0-1,
     // then converted in LDS to the prepared pixels [v v v v v v 0 0], v = 2q - 255 (launch_preprocess's values)
-    const uint64_t up = (uint64_t)p.u8;
-    const v4i32 ur = {(int)(uint32_t)up, (int)((up >> 32) & 0xffff), (int)((size_t)p.B * IH * IH * 3), 0x00020000};
+    const v4i32 ur = buffer_rsrc_words(p.u8, (uint32_t)((size_t)p.B * IH * IH * 3));
     auto dma_raw = [&](int k) {
         if (wave < 2) {
             const int e = 64 * wave + lane, row = 4 * k + 2 + e / 21;
             const bool ok = e < 84 && (unsigned)row < (unsigned)IH;
-            const uint32_t off = ok ? (uint32_t)(((size_t)b * IH + 4 * k + 2) * IH * 3 + 16 * e) : 0x80000000u;
-            dma16(ur, (uint32_t)(uintptr_t)(smem + RAW_OFF + (k & 1) * RAWB + 1024 * wave), off);
+            const uint32_t off = ok ? (uint32_t)(((size_t)b * IH + 4 * k + 2) * IH * 3 + 16 * e) : OOB;
+            dma16_asm(ur, (uint32_t)(uintptr_t)(smem + RAW_OFF + (k & 1) * RAWB + 1024 * wave), off);
         }
     };
     auto convert = [&](int k) {  // thread t: row 4k + 2 + (t >> 7), parity plane (t >> 6) & 1, column index t & 63

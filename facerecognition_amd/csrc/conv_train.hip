@@ -30,21 +30,6 @@ constexpr int KC = 64;  // inner chunk (floats)
 constexpr int LD = KC + 4;
 constexpr int SLD = MT + 1;
 
-__device__ __forceinline__ float xhat(float x, float mean, float rstd) { return __fmul_rn(__fsub_rn(x, mean), rstd); }
-
-// Thread (g, cl) = (tid >> 4, tid & 15): the sum over the 16 row groups of column cl in group order; every thread of
-// the column gets it.  red: 16 x 17 floats.  (head_train.hip's reduction shape.)
-__device__ __forceinline__ float col_sum16(float v, float* red) {
-    const int cl = threadIdx.x & 15, g = threadIdx.x >> 4;
-    __syncthreads();
-    red[g * 17 + cl] = v;
-    __syncthreads();
-    float s = 0.f;
-#pragma unroll
-    for (int k = 0; k < 16; ++k) s += red[k * 17 + cl];
-    return s;
-}
-
 // Output pixel m -> (b, oh, ow).
 struct Pix {
     int b, y, x;

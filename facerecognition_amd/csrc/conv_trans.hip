@@ -23,6 +23,7 @@
 //     hierarchy in the phase loop.
 // HBM per image: x read once (1.6 MB) + y written once (0.4 MB); MFMA per image 2 x 1.18 GFLOP.
 #include "kernels.h"
+#include "lds_dma.h"
 
 #include <hip/hip_ext.h>
 
@@ -50,22 +51,9 @@ constexpr int TRANS_LDS = 163840;         // the whole LDS (padding-lane fragmen
 static_assert(TAB + TAB_B <= TRANS_LDS, "lds");
 constexpr int NPH = OW + 1;               // phases
 constexpr int KS1 = 18, KS2 = 20;         // K-steps: conv1 (9 taps x 2 channel halves), conv2 + downsample
-constexpr uint32_t OOB = 0x80000000u;
 
-// 16-byte LDS-DMA (buffer_load_dwordx4 ... lds; lane l lands at lds_addr + 16 l) from inline asm: the
-// compiler then does not see the LDS write, and its waitcnt pass does not put a vmcnt(0) (the whole DMA)
-// in front of the phase's fragment reads, none of which reads the slots in flight.  The kernel's own waits
-// cover the DMA (m0 is reserved to the compiler, hence the pragma; nothing else here uses m0).
-typedef int v4i32 __attribute__((ext_vector_type(4)));
-#pragma clang diagnostic push
-#pragma clang diagnostic ignored "-Winline-asm"
-__device__ __forceinline__ void dma16(const v4i32& rsrc, uint32_t lds_addr, uint32_t voff) {
-    asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tbuffer_load_dwordx4 %0, %1, 0 offen lds"
-                 :
-                 : "v"(voff), "s"(rsrc), "s"(__builtin_amdgcn_readfirstlane(lds_addr))
-                 : "memory", "m0");
-}
-#pragma clang diagnostic pop
+// The x rows move by dma16_asm: none of a phase's fragment reads touches the slots in flight, and the kernel's own
+// waits cover the DMA.
 
 // acc += w * b with the weight fragment in AGPRs (the whole weight set stays in the accumulator half of the
 // register file for the kernel; hipcc only offers MFMA operands from VGPRs and would copy every fragment
@@ -126,8 +114,7 @@ __global__ __launch_bounds__(256, 1) void trans_kernel(TransArgs p) {
     // ---- x row DMA: row `row` into its slot (row + 1) % 6; rows outside the image read as zeros
     // (the resource spans this image only: 32-bit offsets at any batch size)
     const uint32_t x_bytes = (uint32_t)(TW * TW * TCH * 2);
-    const uint64_t xp = (uint64_t)(p.x + (size_t)b * TW * TW * TCH);
-    const v4i32 xr = {(int)(uint32_t)xp, (int)((xp >> 32) & 0xffff), (int)x_bytes, 0x00020000};
+    const v4i32 xr = buffer_rsrc_words(p.x + (size_t)b * TW * TW * TCH, x_bytes);
     // per piece u (pieces wave + 4 u): the lane's source offset within a row (or OOB for halo columns)
     uint32_t colpart[4];
 #pragma unroll
@@ -145,7 +132,7 @@ __global__ __launch_bounds__(256, 1) void trans_kernel(TransArgs p) {
             const int piece = wave + 4 * u;
             if (piece < XPIECES && piece * 64 + lane < XQ) {
                 const uint32_t off = rin && colpart[u] != OOB ? rbase + colpart[u] : OOB;
-                dma16(xr, (uint32_t)(uintptr_t)(smem + X_OFF + slot * XROW_B + piece * 1024), off);
+                dma16_asm(xr, (uint32_t)(uintptr_t)(smem + X_OFF + slot * XROW_B + piece * 1024), off);
             }
         }
     };
@@ -205,7 +192,7 @@ __global__ __launch_bounds__(256, 1) void trans_kernel(TransArgs p) {
             const uint32_t off = rin && colpart[u & 3] != OOB
                                      ? (uint32_t)(row * TW * TCH * 2) + colpart[u & 3]
                                      : OOB;
-            dma16(xr, (uint32_t)(uintptr_t)(smem + X_OFF + ((row + 1) % XSLOTS) * XROW_B + piece * 1024), off);
+            dma16_asm(xr, (uint32_t)(uintptr_t)(smem + X_OFF + ((row + 1) % XSLOTS) * XROW_B + piece * 1024), off);
         }
     };
     // conv1 epilogue of tile (i, j): PReLU -> bf16 -> the t row's slot

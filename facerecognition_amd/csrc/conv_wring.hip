@@ -21,6 +21,7 @@
 //   * epilogue through an f32 LDS tile (bias or border-class bias, residual, ReLU/PReLU, coalesced
 //     8-channel stores), as conv_igemm.hip.
 #include "kernels.h"
+#include "lds_dma.h"
 
 #include <hip/hip_ext.h>
 
@@ -55,22 +56,8 @@ struct WGeo {
     static constexpr int WP = 2 * (FR_WRING_DEPTH - 1);  // VMEM ops of the prologue's weight loads
     static constexpr int Yb0 = 2 * PPW + 2 * KSS + WP, Yb1 = 2 * PPW + 4 * KSS + WP, Yb = 2 * PPW + 6 * KSS;
     static_assert(Yb0 <= 63 && Yb1 <= 63 && Yb <= 63, "vmcnt field");
-    __device__ static int swz(int row) { return KSS == 2 ? (row >> 1) & 7 : row & 15; }
+    __device__ static int swz_row(int row) { return KSS == 2 ? (row >> 1) & 7 : row & 15; }
 };
-
-template <int N>
-__device__ __forceinline__ void wait_vm() {
-    asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
-}
-constexpr uint32_t OOB = 0x80000000u;
-
-
-typedef __attribute__((address_space(3))) void lds_void;
-
-
-__device__ __forceinline__ void dma16(__amdgpu_buffer_rsrc_t rsrc, const char* lds, uint32_t voff) {
-    __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc, (lds_void*)lds, 16, voff, 0, 0, 0);
-}
 
 template <bool F16, int KSS, int NW>
 __global__ __launch_bounds__(64 * NW, 8 / NW) void conv_wring_kernel(ConvArgs p, int tiles_m) {
@@ -91,12 +78,11 @@ __global__ __launch_bounds__(64 * NW, 8 / NW) void conv_wring_kernel(ConvArgs p,
     // ---- operand B: piece q = wave + NW i (i < PPW) of a stage holds rows RPP q .. RPP q + RPP - 1; the
     // lane's row and its source chunk (the logical chunk stored at its linear destination position)
     const int lrow = lane / NCH;
-    const int cl = (lane % NCH) ^ Gm::swz(RPP * wave + lrow);  // the same for every i
-    const uint32_t x_bytes = (uint32_t)min((size_t)0x7fffffff, (size_t)p.B * p.H * p.W * p.Cx * 2);
-    const __amdgpu_buffer_rsrc_t xr = __builtin_amdgcn_make_buffer_rsrc((void*)p.x, 0, x_bytes, 0x00020000);
-    const __amdgpu_buffer_rsrc_t x2r = __builtin_amdgcn_make_buffer_rsrc(
-        (void*)(p.x2 ? p.x2 : p.x), 0,
-        (uint32_t)min((size_t)0x7fffffff, p.x2 ? (size_t)p.B * p.H2 * p.W2 * p.Cx2 * 2 : (size_t)0), 0x00020000);
+    const int cl = (lane % NCH) ^ Gm::swz_row(RPP * wave + lrow);  // the same for every i
+    const uint32_t x_bytes = clamp31((size_t)p.B * p.H * p.W * p.Cx * 2);
+    const __amdgpu_buffer_rsrc_t xr = buffer_rsrc(p.x, x_bytes);
+    const __amdgpu_buffer_rsrc_t x2r =
+        buffer_rsrc(p.x2 ? p.x2 : p.x, clamp31(p.x2 ? (size_t)p.B * p.H2 * p.W2 * p.Cx2 * 2 : (size_t)0));
     const int HoWo = p.Ho * p.Wo;
     int a_ih[PPW], a_iw[PPW];
     uint32_t a_base[PPW], a_base2[PPW];
@@ -156,8 +142,7 @@ __global__ __launch_bounds__(64 * NW, 8 / NW) void conv_wring_kernel(ConvArgs p,
     };
 
     // ---- operand A: packed weights, lane (n = 16 i + (lane & 15) of the wave's 32, group lane >> 4)
-    const __amdgpu_buffer_rsrc_t wr = __builtin_amdgcn_make_buffer_rsrc(
-        (void*)p.wimg, 0, (uint32_t)min((size_t)0x7fffffff, (size_t)p.Kpad * p.Npad * 2), 0x00020000);
+    const __amdgpu_buffer_rsrc_t wr = buffer_rsrc(p.wimg, clamp31((size_t)p.Kpad * p.Npad * 2));
     const uint32_t wvo = (uint32_t)(((lane >> 4) * p.Npad + n0 + 32 * wave + (lane & 15)) * 16);
     const uint32_t wstep = (uint32_t)(64 * p.Npad);  // bytes per substep image
     constexpr int WD = FR_WRING_DEPTH;
@@ -173,7 +158,7 @@ __global__ __launch_bounds__(64 * NW, 8 / NW) void conv_wring_kernel(ConvArgs p,
     int boff[KSS];
 #pragma unroll
     for (int kk = 0; kk < KSS; ++kk)
-        boff[kk] = (lane & 15) * ROWB + ((4 * kk + (lane >> 4)) ^ Gm::swz(lane & 15)) * 16;
+        boff[kk] = (lane & 15) * ROWB + ((4 * kk + (lane >> 4)) ^ Gm::swz_row(lane & 15)) * 16;
     frag bq[2][FM];
     auto bread = [&](frag (&b)[FM], int slot, int kk) {
         const char* a = smem + slot * STAGE_B + boff[kk];

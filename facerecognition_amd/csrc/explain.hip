@@ -20,21 +20,6 @@ constexpr int HG_WAVES = 8;     // waves of a workgroup: each sums its own eight
 constexpr int HG_KB = 512;      // K columns per workgroup: 64 lanes x 8 consecutive columns (one 16-B load per row)
 constexpr int HG_NMAX = 1024;   // G tile [HG_BT][N] in LDS
 
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    return v;
-}
-
-// sum over 256 threads; red: 4 floats of LDS (reused: a barrier on both sides)
-__device__ __forceinline__ float block_sum4(float v, float* red) {
-    v = wave_sum(v);
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-    __syncthreads();
-    return red[0] + red[1] + red[2] + red[3];
-}
-
 // One workgroup per image.
 __global__ __launch_bounds__(256) void score_grad_kernel(const float* __restrict__ emb, const float* __restrict__ target,
                                                          int N, float* __restrict__ g) {
@@ -53,9 +38,9 @@ __global__ __launch_bounds__(256) void score_grad_kernel(const float* __restrict
         tt += b * b;
         et += a * b;
     }
-    ee = block_sum4(ee, red);
-    tt = block_sum4(tt, red);
-    et = block_sum4(et, red);
+    ee = block_sum_256(ee, red);
+    tt = block_sum_256(tt, red);
+    et = block_sum_256(et, red);
     const float ne = fmaxf(sqrtf(ee), 1e-8f), nt = fmaxf(sqrtf(tt), 1e-8f);
     const float ca = 1.0f / (ne * nt), cb = et / (ne * ne * ne * nt);
     for (int n = threadIdx.x; n < N; n += 256) out[n] = t[n] * ca - e[n] * cb;

@@ -50,8 +50,6 @@ __device__ __forceinline__ uint4 mask_words(const HeadArgs& a, uint64_t i) {
                          make_uint2((uint32_t)a.seed, (uint32_t)(a.seed >> 32)));
 }
 
-__device__ __forceinline__ float xhat(float x, float mean, float rstd) { return __fmul_rn(__fsub_rn(x, mean), rstd); }
-
 // A[b][k .. k + 3] (k % 4 == 0): the input BN's affine on x^, then the dropout mask.
 __device__ __forceinline__ float4 head_a4(const HeadArgs& a, int64_t b, int k) {
     float4 v = *(const float4*)(a.X + (size_t)b * a.K + k);
@@ -89,19 +87,6 @@ __device__ __forceinline__ float block_sum256(float v, float* red) {
         __syncthreads();
     }
     return red[0];
-}
-
-// Thread (g, cl) = (tid >> 4, tid & 15): the sum over the 16 row groups of column cl in group order; every thread of
-// the column gets it.  red: 16 x 17 floats.
-__device__ __forceinline__ float col_sum16(float v, float* red) {
-    const int cl = threadIdx.x & 15, g = threadIdx.x >> 4;
-    __syncthreads();
-    red[g * 17 + cl] = v;
-    __syncthreads();
-    float s = 0.f;
-#pragma unroll
-    for (int k = 0; k < 16; ++k) s += red[k * 17 + cl];
-    return s;
 }
 
 struct BnOut {

@@ -158,8 +158,9 @@ __global__ __launch_bounds__(256, 1) void match_p512_kernel(const float* __restr
     }
 
     // the split's rows as a buffer resource: rows past the split read 0 (out of range)
+    // (buffer_rsrc_words' four words, written out: through the builder hipcc orders this scalar code differently)
     const uint64_t gp = (uint64_t)(G + (size_t)g_begin * D512);
-    const v4i32 gr = {(int)(uint32_t)gp, (int)((gp >> 32) & 0xffff), rows * D512 * 4, 0x00020000};
+    const v4i32 gr = {(int)(uint32_t)gp, (int)((gp >> 32) & 0xffff), rows * D512 * 4, RSRC_WORD3};
     const uint32_t smem_base = (uint32_t)(uintptr_t)smem;
     // chunk c = (tile c / 8, floats 64 (c % 8) ..) into ring buffer c % NBUF: wave w issues pieces w + 4u,
     // piece q = rows 4q .. 4q + 3, lane -> row 4q + (lane >> 4), slot lane & 15 = column group

@@ -27,6 +27,7 @@
 // sets the stream rate (in flight / L2 latency).  Blocks of one gallery split share an XCD (xcd_remap), so each XCD streams its
 // splits from HBM once and the other probe blocks hit its L2.
 #include "kernels.h"
+#include "lds_dma.h"
 
 #include <algorithm>
 #include <float.h>
@@ -61,10 +62,6 @@ constexpr float X_ACC = 2048.f / 16777216.f;  // c of the header: f32 accumulati
 // header of the chunk buffer (elements; 8 KiB keeps the chunks 8-KiB aligned): uint32 [0] = EG, [1] = GN as
 // f32 bits (non-negative: integer max == float max), raised by every split_x3_kernel launch
 constexpr int X3_HEAD = 4096;
-
-__device__ __forceinline__ bool better(float s1, int i1, float s2, int i2) {
-    return s1 > s2 || (s1 == s2 && i1 < i2);
-}
 
 template <int KMAX>
 __device__ __forceinline__ void insert(float (&ls)[KMAX], int (&li)[KMAX], float s, int idx) {
@@ -159,7 +156,6 @@ constexpr int XCHUNK_B = XG * XC * 2;          // 8 KiB: [64 rows x 128 B]
 static_assert(XCHUNK_B == XCHUNK_E * 2, "chunk layout");
 constexpr int XRB = XC * 2;                    // LDS row bytes
 constexpr int XPPW = XCHUNK_B / 1024 / 8;      // 1-KiB DMA pieces per wave per chunk
-typedef __attribute__((address_space(3))) void lds_void;
 
 __device__ __forceinline__ int xswz(int row, int chunk) { return chunk ^ xswz_row(row); }
 
@@ -211,8 +207,7 @@ __global__ __launch_bounds__(512) void match_x3_kernel(const float* __restrict__
     // (32-bit offsets); look-ahead chunks past the gallery read 0, past the split are never used.
     const size_t g_chunk0 = (size_t)(g_begin / XG) * XNC;
     const size_t g_left = ((size_t)((N + XG - 1) / XG) * XNC - g_chunk0) * XCHUNK_B;
-    const __amdgpu_buffer_rsrc_t rg = __builtin_amdgcn_make_buffer_rsrc((void*)(GT + g_chunk0 * XCHUNK_E), 0,
-                                                                        (int)min(g_left, (size_t)0x7fffffff), 0x00020000);
+    const __amdgpu_buffer_rsrc_t rg = buffer_rsrc(GT + g_chunk0 * XCHUNK_E, clamp31(g_left));
     auto issue_chunk = [&](int64_t t0, int c, int slot) {
         const uint32_t cbase = (uint32_t)((((t0 - g_begin) / XG) * XNC + c) * XCHUNK_B);
 #pragma unroll

@@ -134,16 +134,6 @@ __global__ __launch_bounds__(256) void avgpool_kernel(const bf16_t* __restrict__
     *(uint4*)(y + (size_t)b * C + g * 8) = Num<F16>::pack8(acc);
 }
 
-__device__ __forceinline__ float block_sum_256(float v, float* red) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    __syncthreads();
-    if (lane == 0) red[wave] = v;
-    __syncthreads();
-    return red[0] + red[1] + red[2] + red[3];
-}
-
 // One block per row: out[b][n] = sum_s partial[s][b][n] + bias[n]; optional L2 normalize.  N % 4 == 0 and
 // N <= 1024 (the launcher checks): a thread owns 4 consecutive columns, float4 loads, the split loop
 // unrolled so its loads are in flight together.

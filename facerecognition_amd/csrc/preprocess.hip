@@ -24,13 +24,6 @@
 namespace fr {
 namespace {
 
-constexpr int PB = 22;  // Pillow PRECISION_BITS (32 - 8 - 2)
-
-__device__ __forceinline__ uint8_t clip8(int v) {
-    v >>= PB;  // arithmetic shift: floor, as Pillow's clip8 lookup
-    return (uint8_t)(v < 0 ? 0 : (v > 255 ? 255 : v));
-}
-
 // horizontal pass: tmp[b][r][x][c] for source rows r0 .. r0 + rows - 1
 __global__ __launch_bounds__(256) void resize_h_kernel(const uint8_t* __restrict__ in, int B, int H, int W,
                                                        int r0, int rows, int OW, const int32_t* __restrict__ bounds,

@@ -17,6 +17,7 @@
 // A new consumer of exact scores includes this header; it does not copy a loop.  Device code only, no host state.
 #pragma once
 #include "kernels.h"
+#include "lds_dma.h"
 
 namespace fr {
 namespace tile {  // consumers say `using namespace tile;` inside namespace fr
@@ -27,11 +28,6 @@ constexpr int MG = MT;       //  gallery rows per tile)
 constexpr int KC = 64;       // inner-dimension chunk (floats)
 constexpr int LD = KC + 4;   // row stride of a staged operand tile in LDS
 constexpr int SLD = MT + 1;  // row stride of a score tile in LDS
-
-// The total order of the match results: score descending, index ascending.
-__device__ __forceinline__ bool better(float s1, int i1, float s2, int i2) {
-    return s1 > s2 || (s1 == s2 && i1 < i2);
-}
 
 // One 16-float step of one accumulator: x y z w.
 __device__ __forceinline__ void mfma_k4(f32x4_t& acc, const float4& a4, const float4& b4) {
@@ -152,21 +148,8 @@ constexpr int CHUNK_B = MG * KC * 4;                 // 16384
 constexpr int P512_LDS = NBUF * CHUNK_B + MP * SLD * 4;  // [NBUF chunks][score tile]
 constexpr int P512_MAX_TILES = 64;                   // per split: the DMA offsets are 32-bit
 
-__device__ __forceinline__ void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
-
-// 16-B LDS-DMA from inline asm (lane l lands at lds_addr + 16 l): the compiler does not see the LDS write, so it
-// adds no vmcnt(0) before later LDS accesses; p512_tile's own counted waits cover it
-typedef int v4i32 __attribute__((ext_vector_type(4)));
-#pragma clang diagnostic push
-#pragma clang diagnostic ignored "-Winline-asm"
-__device__ __forceinline__ void dma16_asm(const v4i32& rsrc, uint32_t lds_addr, uint32_t voff) {
-    asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tbuffer_load_dwordx4 %0, %1, 0 offen lds"
-                 :
-                 : "v"(voff), "s"(rsrc), "s"(__builtin_amdgcn_readfirstlane(lds_addr))
-                 : "memory", "m0");
-}
-#pragma clang diagnostic pop
-
+// The ring moves by dma16_asm (lds_dma.h): p512_tile's own counted waits cover it.
+//
 // A kernel's sweep of one gallery split is put together from the pieces below, in this order (eval_p512_kernel is
 // the plainest example):
 //     float4 pa[D512 / 16];
@@ -230,8 +213,9 @@ struct P512Ring {
 // Gs: the split's first row; rows <= 64 P512_MAX_TILES; smem: the block's P512_LDS bytes of dynamic LDS.  Issues the
 // first NBUF - 1 chunks.
 __device__ __forceinline__ P512Ring p512_ring_start(const float* __restrict__ Gs, int rows, char* smem) {
+    // buffer_rsrc_words' four words, written out: through the builder hipcc orders this scalar code differently
     const uint64_t gp = (uint64_t)Gs;
-    const P512Ring ring = {{(int)(uint32_t)gp, (int)((gp >> 32) & 0xffff), rows * D512 * 4, 0x00020000},
+    const P512Ring ring = {{(int)(uint32_t)gp, (int)((gp >> 32) & 0xffff), rows * D512 * 4, RSRC_WORD3},
                            (uint32_t)(uintptr_t)smem};
 #pragma unroll
     for (int c = 0; c < NBUF - 1; ++c) ring.issue_chunk(c);

@@ -49,16 +49,6 @@ constexpr int SCAN_T = 1024;
 
 typedef float f2 __attribute__((ext_vector_type(2)));
 
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-    for (int o = 32; o; o >>= 1) v += __shfl_xor(v, o);
-    return v;
-}
-__device__ __forceinline__ double wave_sum(double v) {
-#pragma unroll
-    for (int o = 32; o; o >>= 1) v += __shfl_xor(v, o);
-    return v;
-}
 __device__ __forceinline__ float wave_min(float v) {
 #pragma unroll
     for (int o = 32; o; o >>= 1) v = fminf(v, __shfl_xor(v, o));
