@@ -47,9 +47,17 @@ def __getattr__(name):  # lazy: importing the package must not initialise the GP
     if name in _AUGMENT:
         from . import augment
         return getattr(augment, name)
+    if name in _OPTIM:
+        from . import optim
+        return getattr(optim, name)
+    if name in _TRAINER:
+        from . import trainer
+        return getattr(trainer, name)
     raise AttributeError(name)
 
 
+_OPTIM = ("SGD", "Adam", "AdamW")
+_TRAINER = ("ArcFaceTrainer", "EarlyStopping")
 _AUGMENT = ("get_train_transforms", "get_val_transforms", "facenet_train_transforms", "DeviceTransform", "mixup_data")
 _HEAD = ("EmbeddingHead",)
 _BACKBONE_TRAIN = ("Bottleneck", "ResNet50Layer4")

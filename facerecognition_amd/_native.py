@@ -31,6 +31,14 @@ FR_CONV_IN_RELU = 1
 FR_BN_BATCH_STATS = 1
 FR_BN_RELU = 2
 FR_CUT_LAYER4_IN = 0
+FR_OPTIM_SGD, FR_OPTIM_ADAM, FR_OPTIM_ADAMW = 0, 1, 2
+FR_OPTIM_NESTEROV = 1
+FR_OPTIM_MAXIMIZE = 2
+FR_OPTIM_AMSGRAD = 4
+FR_OPTIM_SKIP_NONFINITE = 8
+FR_OPTIM_CHUNK = 65536
+FR_OPTIM_MAX_GROUPS = 32
+FR_ERR_ARG = -1
 FR_ERR_STAGE = -6
 FR_TILE_BAND = 7
 FR_TILE_IMG28 = 10
@@ -210,6 +218,12 @@ _SIGS = {
     "fr_augment_workspace": (c_size_t, [c_int, c_int]),
     "fr_augment": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p,
                            c_size_t, c_void_p]),
+    "fr_optim_workspace": (c_size_t, [c_int64]),
+    "fr_optim_grad_norm": (c_int, [c_void_p, c_void_p, c_int, ctypes.c_double, c_int, c_void_p, c_void_p, c_int,
+                                   c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "fr_optim_step": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int,
+                              ctypes.c_double, ctypes.c_double, ctypes.c_double, ctypes.c_double, ctypes.c_double,
+                              ctypes.c_double, ctypes.c_double, c_int, c_void_p, c_int, c_void_p, c_void_p]),
     "fr_op_preprocess": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_int, c_void_p]),
     "fr_op_maxpool": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p,
                               c_int, c_int, c_int, c_int, c_int, c_void_p]),

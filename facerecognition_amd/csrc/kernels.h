@@ -522,4 +522,43 @@ size_t augment_lds_bytes(int H, int W);
 hipError_t launch_augment(const uint8_t* in, int B, int H, int W, const int32_t* ops, const double* args, int n_ops,
                           const float* norm, float* out_f32, uint8_t* out_u8, hipStream_t s);
 
+// Optimiser step (optim.hip; DESIGN.md §4 "Optimiser step and training loop").  Arguments are checked by optim_api.cpp;
+// every launcher only enqueues on s.  The tensor tables travel in the kernel arguments, one launch per table; chunk0
+// is the exclusive prefix sum of the tensors' chunk counts inside the launch (chunk0[n] = the grid).
+constexpr int FR_OPTIM_STEP_CHUNK = 16384;  // elements one workgroup of the update pass owns
+constexpr int OPTIM_NORM_TENSORS = 64;
+constexpr int OPTIM_STEP_TENSORS = 48;
+constexpr int OPTIM_MAX_GROUPS = 32;  // = FR_OPTIM_MAX_GROUPS
+struct OptimNormTable {
+    const float* g[OPTIM_NORM_TENSORS];
+    int64_t numel[OPTIM_NORM_TENSORS];
+    int32_t chunk0[OPTIM_NORM_TENSORS + 1];
+    int n;
+};
+struct OptimStepTable {
+    float* p[OPTIM_STEP_TENSORS];
+    const float* g[OPTIM_STEP_TENSORS];
+    float* s1[OPTIM_STEP_TENSORS];  // momentum_buffer / exp_avg
+    float* s2[OPTIM_STEP_TENSORS];  // exp_avg_sq
+    int64_t numel[OPTIM_STEP_TENSORS];
+    int64_t born[OPTIM_STEP_TENSORS];
+    int32_t chunk0[OPTIM_STEP_TENSORS + 1];
+    int n;
+};
+struct OptimGroupBetas {
+    double beta1[OPTIM_MAX_GROUPS], beta2[OPTIM_MAX_GROUPS];
+    int n;
+};
+struct OptimHyper {
+    double lr, weight_decay, momentum, dampening, beta1, beta2, eps;
+    int flags;
+};
+hipError_t launch_optim_sumsq(const OptimNormTable& t, int64_t chunk_base, const float* grad_scale, double* partials,
+                              hipStream_t s);
+hipError_t launch_optim_norm_finish(const double* partials, int64_t n_chunks, float max_norm, bool skip_nonfinite,
+                                    const float* found_inf, const OptimGroupBetas& betas, int64_t attempt, void* ctrl,
+                                    hipStream_t s);
+hipError_t launch_optim_step(int kind, const OptimStepTable& t, const OptimHyper& h, const void* ctrl, int group,
+                             const float* grad_scale, hipStream_t s);
+
 }  // namespace fr

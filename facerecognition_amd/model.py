@@ -62,6 +62,14 @@ class FRModel:
         buf = ctypes.create_string_buffer(blob, len(blob))
         N.check(N.lib().fr_load_weights(self._h, buf, len(blob)), "fr_load_weights")
         self.embedding_size = N.lib().fr_embed_dim(self._h)
+        self._state_dict = dict(state_dict)  # the unfolded values, for state_dict()
+
+    def state_dict(self) -> dict:
+        """The state_dict last loaded (the reference's key names, unfolded; a shallow copy).  The trainer takes the
+        frozen trunk's values from it."""
+        if getattr(self, "_state_dict", None) is None:
+            raise RuntimeError("FRModel.state_dict: no weights loaded")
+        return dict(self._state_dict)
 
     def set_option(self, option: int, value: int) -> None:
         """fr_set_option (FR_OPT_STAGE, FR_OPT_KEEP_INTERMEDIATES; include/frhip.h)."""

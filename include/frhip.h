@@ -698,6 +698,78 @@ int fr_bn_act_backward(const float* dY, const float* Z, int64_t M, int C, const 
                        float* dZ /*NULL*/, float* dRes /*NULL*/, float* dgamma /*NULL*/, float* dbeta /*NULL*/,
                        void* stream);
 
+/* ---- Optimiser step: torch's clip_grad_norm_ followed by SGD, Adam or AdamW over a list of f32 device tensors, in
+ *      two stages and without a host round trip.  Handle-free, caller-owned buffers, the caller's stream.  The arrays
+ *      of pointers, counts and betas are host arrays, read during the call: the tensor table travels in kernel
+ *      arguments (64 tensors per norm launch, 48 per update launch), so nothing of it can go stale.  A tensor whose
+ *      gradient pointer is NULL or whose element count is 0 is skipped, in both stages alike.
+ *      Stage 1, fr_optim_grad_norm: g' = g / *grad_scale (grad_scale non-NULL; f32 division) else g.  Every gradient is
+ *        cut into chunks of FR_OPTIM_CHUNK elements; chunk c (counted over the whole list) gets sum g'^2 of its
+ *        elements in ws[c] (double; fixed order), one workgroup adds ws[0 .. n_chunks) in a fixed order, and
+ *        norm = (float)sqrt(sum).  The norm is a function of the tensor list alone: not of the launches the list is
+ *        cut into, of the pointers' alignment or of ws_bytes.  No floating-point atomics.  The same workgroup writes
+ *        the control block ctrl (device, FR_OPTIM_CTRL_BYTES(n_groups), 8-byte aligned; the host never reads it in a
+ *        step): head.norm; head.clip = min(1, max_norm / (norm + 1e-6f)) in f32 -- torch's rule, a NaN norm giving NaN
+ *        -- or 1 when max_norm <= 0 (no clipping; the norm is still reported); head.skip = (*found_inf != 0, found_inf
+ *        non-NULL) or (FR_OPTIM_SKIP_NONFINITE and the norm is not finite).  Unless skip, every group state
+ *        g < n_groups advances: step += 1, beta1_pow *= beta1[g], beta2_pow *= beta2[g] (doubles), prev_ok = last_ok,
+ *        last_ok = attempt.  attempt >= 1 is the caller's count of fr_optim_grad_norm calls on this block, rising by
+ *        at least one per call.  A fresh block is zero except beta1_pow = beta2_pow = 1.
+ *      Stage 2, fr_optim_step, one group's tensors in one pass (p, g and the state read once, p and the state written
+ *        once; 16-byte accesses through every pointer that is 16-byte aligned, 4-byte ones through one that is not
+ *        -- a view at a storage offset -- and for the last numel % 4 elements).  With head.skip set nothing is
+ *        written: parameters, state and counters keep every byte.  Otherwise, every operation rounded to f32 (no
+ *        fused multiply-add), sqrt and / correctly rounded, Python-double hyper-parameters cast to f32 where torch's
+ *        kernels take them, in torch's single-tensor order:
+ *          g = (g / *grad_scale) * head.clip;  FR_OPTIM_MAXIMIZE: g = -g
+ *          SGD:   wd != 0: g = g + wd p;  momentum != 0: buf = g in the tensor's first applied step (prev_ok < born[i]),
+ *                 else buf = buf momentum + (1 - dampening) g;  g = nesterov ? g + momentum buf : buf;  p = p + (-lr) g
+ *          Adam:  wd != 0: g = g + wd p;   AdamW: wd != 0: p = p (1 - lr wd)
+ *                 d = g - m, w = 1 - beta1: m = w < 0.5 ? m + w d : g - d (1 - w);  v = v beta2 + ((1 - beta2) g) g
+ *                 denom = sqrt(v) / sqrt(1 - beta2_pow) + eps;  p = p + (-(lr / (1 - beta1_pow)) m) / denom
+ *        state1 is momentum_buffer / exp_avg, state2 exp_avg_sq; born[i] is the attempt at which tensor i's state was
+ *        created (0: it was loaded, the buffer is live).  amsgrad (FR_OPTIM_AMSGRAD) is refused.
+ *      Limits, each FR_ERR_ARG with a message before any HIP call: n_tensors >= 0 with non-NULL arrays when > 0; every
+ *      numel in [0, 2^40], at most 2^24 chunks per call; pointers 4-byte aligned; max_norm not NaN; n_groups in
+ *      [0, FR_OPTIM_MAX_GROUPS], group < FR_OPTIM_MAX_GROUPS; betas in [0, 1); lr, eps, weight_decay, momentum >= 0 and
+ *      finite, dampening finite; nesterov needs momentum > 0 and dampening = 0; no unknown flag bits; kind one of the
+ *      three; a parameter and the state the kind needs non-NULL for every tensor with a gradient; ctrl and ws
+ *      non-NULL and 8-byte aligned; ws_bytes >= fr_optim_workspace(n_chunks); attempt >= 1. ---- */
+#define FR_OPTIM_SGD 0
+#define FR_OPTIM_ADAM 1
+#define FR_OPTIM_ADAMW 2
+#define FR_OPTIM_NESTEROV 1
+#define FR_OPTIM_MAXIMIZE 2
+#define FR_OPTIM_AMSGRAD 4        /* refused */
+#define FR_OPTIM_SKIP_NONFINITE 8 /* fr_optim_grad_norm only */
+#define FR_OPTIM_CHUNK 65536
+#define FR_OPTIM_MAX_GROUPS 32
+typedef struct fr_optim_ctrl_head {
+    float norm, clip;
+    int32_t skip;
+    int32_t reserved[13];
+} fr_optim_ctrl_head; /* 64 bytes */
+typedef struct fr_optim_group_state {
+    double step, beta1_pow, beta2_pow;
+    int64_t last_ok, prev_ok;
+    int64_t reserved[3];
+} fr_optim_group_state; /* 64 bytes */
+#define FR_OPTIM_CTRL_BYTES(n_groups) (64 * (1 + (size_t)(n_groups)))
+
+/* Bytes of device workspace fr_optim_grad_norm needs for n_chunks = sum over the tensors with a gradient of
+ * ceil(numel / FR_OPTIM_CHUNK) chunks (0 and a message on bad arguments; never 0 otherwise). */
+size_t fr_optim_workspace(int64_t n_chunks);
+int fr_optim_grad_norm(const float* const* grads /*host [n_tensors]*/, const int64_t* numel /*host [n_tensors]*/,
+                       int n_tensors, double max_norm, int flags, const float* found_inf /*device, NULL*/,
+                       const float* grad_scale /*device, NULL*/, int n_groups, const double* beta1 /*host [n_groups]*/,
+                       const double* beta2 /*host [n_groups]*/, int64_t attempt, void* ctrl, void* ws, size_t ws_bytes,
+                       void* stream);
+int fr_optim_step(int kind, float* const* params, const float* const* grads, float* const* state1 /*NULL*/,
+                  float* const* state2 /*NULL*/, const int64_t* numel, const int64_t* born /*NULL: all 0*/, int n_tensors,
+                  double lr, double weight_decay, double momentum, double dampening, double beta1, double beta2,
+                  double eps, int flags, const void* ctrl, int group, const float* grad_scale /*device, NULL*/,
+                  void* stream);
+
 /* ---- op-level entry points (kernel parity tests and custom graphs) ---- */
 
 /* Implicit-GEMM convolution on NHWC bf16 with fused epilogue:
