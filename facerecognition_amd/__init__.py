@@ -50,12 +50,19 @@ def __getattr__(name):  # lazy: importing the package must not initialise the GP
     if name in _OPTIM:
         from . import optim
         return getattr(optim, name)
+    if name in _DETECT:
+        from . import face_detector
+        return getattr(face_detector, name)
+    if name == "RecognitionEngine":
+        from .recognition_engine import RecognitionEngine
+        return RecognitionEngine
     if name in _TRAINER:
         from . import trainer
         return getattr(trainer, name)
     raise AttributeError(name)
 
 
+_DETECT = ("FaceDetector", "DeviceMTCNN", "detect_face", "synth_mtcnn_state", "load_mtcnn_state")
 _OPTIM = ("SGD", "Adam", "AdamW")
 _TRAINER = ("ArcFaceTrainer", "EarlyStopping")
 _AUGMENT = ("get_train_transforms", "get_val_transforms", "facenet_train_transforms", "DeviceTransform", "mixup_data")

@@ -159,6 +159,18 @@ _SIGS = {
     "fr_mtcnn_dense": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p]),
     "fr_mtcnn_head": (c_int, [c_void_p, c_int64, c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p]),
     "fr_nms_host": (c_int, [c_void_p, c_int64, c_void_p, ctypes.c_float, c_int, c_void_p, c_void_p]),
+    "fr_nms_workspace": (c_size_t, [c_int64, c_int64]),
+    "fr_nms": (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_int64, ctypes.c_float, c_int, c_void_p, c_void_p,
+                       c_void_p, c_size_t, c_void_p]),
+    "fr_mtcnn_compact_workspace": (c_size_t, [c_int64]),
+    "fr_mtcnn_candidates": (c_int, [c_void_p, c_int, c_int, c_int, ctypes.c_float, ctypes.c_float, c_int, c_int64,
+                                    c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "fr_mtcnn_select": (c_int, [c_void_p, c_int64, c_int, ctypes.c_float, c_void_p, c_void_p, c_void_p, c_void_p,
+                                c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "fr_mtcnn_crop_boxes": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_void_p, c_void_p, c_int,
+                                    c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t,
+                                    c_void_p]),
+    "fr_mtcnn_final_boxes": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p]),
     "fr_lbph_table": (c_int, [c_int, c_int, c_void_p, c_void_p]),
     "fr_lbph_hist": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
     "fr_lbph_match_workspace": (c_size_t, [c_int, c_int64, c_int, c_int]),

@@ -7,8 +7,9 @@ Reference → here:
       cv2.warpAffine(image, M, (112, 112), borderValue=0)     -> fr_warp_affine_u8 (device, batched)
   get_transform / get_facenet_transform Resize (extract_embeddings.py:170-185):
       PIL Image.resize((S, S), Image.BILINEAR)                -> fr_resize_u8 (device, batched, PIL-exact)
-The landmark detector (MTCNN) stays out of scope: landmarks come from the caller, as the reference's
-align_face receives them."""
+Landmarks come from the caller, as the reference's align_face receives them; the device MTCNN that finds them
+is face_detector.py (``FaceDetector.detect`` / ``detect_batch``), and ``RecognitionEngine.recognize_frames``
+feeds a batch of its detections to one ``align_faces`` launch."""
 from __future__ import annotations
 
 from typing import Dict, Sequence

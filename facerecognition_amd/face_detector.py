@@ -7,7 +7,9 @@ to ``ARCFACE_TEMPLATE`` (inference/recognition_engine.py:169-242).  Here the P/R
 and the box crops run on the device through libfrhip.so (mtcnn.hip: f32 area resampling bit-identical to
 torch, f32 convs / pools / dense layers / heads); the per-stage box bookkeeping -- thresholding,
 non-maximum suppression, box regression, squaring and padding, a few hundred boxes -- is host logic, as
-in the reference, whose last NMS is numpy as well (``detect_face``'s ``batched_nms_numpy``).  The
+in the reference, whose last NMS is numpy as well (``detect_face``'s ``batched_nms_numpy``).
+``DeviceMTCNN.detect_batch`` takes a batch of equal-size frames and keeps the boxes on the device from the
+P-net map to the O-net output (nms_device.hip, mtcnn_boxes.hip), bit-identical to the host logic.  The
 alignment warp is ``align.align_faces`` (device, OpenCV's fixed-point warpAffine).
 
 Weights: facenet-pytorch's pretrained pnet.pt / rnet.pt / onet.pt are not in the reference or this
@@ -299,13 +301,19 @@ class DeviceMTCNN:
     load_mtcnn_state layout) as f32 NHWC launches of mtcnn.hip."""
 
     def __init__(self, state: Dict[str, np.ndarray], device: int = 0, min_face_size: int = MIN_FACE,
-                 thresholds: Sequence[float] = THRESHOLDS, factor: float = FACTOR, select_largest: bool = True):
+                 thresholds: Sequence[float] = THRESHOLDS, factor: float = FACTOR, select_largest: bool = True,
+                 capacity: int = 1 << 17):
+        """capacity: rows of detect_batch's P-net candidate buffer (all levels and frames of one call; the
+        calibrated weights pass ~3,600 per 1080p frame).  A call that passes more finishes on the host path."""
         import torch
         if not torch.cuda.is_available():
             raise RuntimeError("DeviceMTCNN needs a ROCm GPU; there is deliberately no CPU fallback")
         self.device = torch.device("cuda", device)
         self.min_face_size, self.thresholds, self.factor = min_face_size, tuple(thresholds), factor
         self.select_largest = select_largest
+        if int(capacity) < 1:
+            raise ValueError("capacity must be positive")
+        self.capacity = int(capacity)
         dev = self.device
 
         def t(a):
@@ -414,6 +422,182 @@ class DeviceMTCNN:
         return detect_face(imgs, self.resample, self.pnet, self.rnet, self.onet, self.min_face_size,
                            self.thresholds, self.factor)
 
+    # -- detect_batch: the box logic on the device ----------------------------------------------
+    def _resample_dev(self, imgs_dev, regions_dev, n: int, oh: int, ow: int):
+        """resample() with the regions (int32 [>= n, 5]) already in device memory."""
+        import torch
+        _, H, W, _ = imgs_dev.shape
+        out = torch.empty((n, oh, ow, 3), dtype=torch.float32, device=self.device)
+        N.check(N.lib().fr_area_resample_u8(N.ptr(imgs_dev), H, W, N.ptr(regions_dev), n, oh, ow, N.ptr(out),
+                                            self._s()), "fr_area_resample_u8")
+        return out
+
+    def _compact_ws(self, total: int):
+        import torch
+        nb = N.lib().fr_mtcnn_compact_workspace(total)
+        return torch.empty((max(nb, 4),), dtype=torch.uint8, device=self.device), nb
+
+    def _nms_dev(self, box, n: int, score, sid, valid, src, n_seg: int, thresh: float):
+        """One fr_nms call over positions 0..n-1 cut into n_seg segments: position p (used when valid[p]) belongs
+        to segment sid[p], has score[p] and stands for box row src[p] (None: p).  Inside a segment the visiting
+        order is score descending, the lower position first among equal scores (np.argsort(-s, kind="stable")):
+        one stable sort of the int64 keys (segment << 32 | ~score bits) -- the bits of a non-negative float32
+        order as the floats do.  Returns (keep [n] int64: box rows, segment by segment; seg_kept [n_seg + 1])."""
+        import torch
+        dev = self.device
+        bits = score.contiguous().view(torch.int32).to(torch.int64)
+        key = torch.where(valid, (sid.to(torch.int64) << 32) | (0xFFFFFFFF - bits),
+                          torch.full((), 2 ** 63 - 1, dtype=torch.int64, device=dev))
+        skey, perm = torch.sort(key, stable=True)
+        order = (perm if src is None else src[perm]).contiguous()
+        seg_start = torch.searchsorted(skey >> 32, torch.arange(n_seg + 1, dtype=torch.int64, device=dev)).contiguous()
+        keep = torch.zeros((n,), dtype=torch.int64, device=dev)
+        seg_kept = torch.zeros((n_seg + 1,), dtype=torch.int64, device=dev)
+        nws = N.lib().fr_nms_workspace(n, n_seg)
+        ws = torch.empty((nws,), dtype=torch.uint8, device=dev)
+        N.check(N.lib().fr_nms(N.ptr(box), n, N.ptr(order), N.ptr(seg_start), n_seg, float(thresh), 0, N.ptr(keep),
+                               N.ptr(seg_kept), N.ptr(ws), nws, self._s()), "fr_nms")
+        return keep, seg_kept
+
+    def _crop_boxes(self, box, score, reg, img, n, B, keep, seg_kept, n_seg, plus1, W, H, counter_ptr):
+        import torch
+        dev = self.device
+        obox = torch.empty((n, 4), dtype=torch.float32, device=dev)
+        oscore = torch.zeros((n,), dtype=torch.float32, device=dev)
+        oimg = torch.zeros((n,), dtype=torch.int32, device=dev)
+        regions = torch.empty((n, 5), dtype=torch.int32, device=dev)
+        ws, nws = self._compact_ws(n)
+        N.check(N.lib().fr_mtcnn_crop_boxes(N.ptr(box), N.ptr(score), N.ptr(reg), N.ptr(img), n, B, N.ptr(keep),
+                                            N.ptr(seg_kept) + 8 * n_seg, plus1, W, H, N.ptr(obox), N.ptr(oscore),
+                                            N.ptr(oimg), N.ptr(regions), counter_ptr, N.ptr(ws), nws, self._s()),
+                "fr_mtcnn_crop_boxes")
+        return obox, oscore, oimg, regions
+
+    def _select(self, out, n, thresh, box, img, counter_ptr):
+        import torch
+        dev, C = self.device, int(out.shape[1])
+        obox = torch.empty((n, 4), dtype=torch.float32, device=dev)
+        oscore = torch.zeros((n,), dtype=torch.float32, device=dev)
+        oreg = torch.empty((n, 4), dtype=torch.float32, device=dev)
+        oimg = torch.zeros((n,), dtype=torch.int32, device=dev)
+        opts = torch.empty((n, 10), dtype=torch.float32, device=dev) if C == 16 else None
+        ws, nws = self._compact_ws(n)
+        N.check(N.lib().fr_mtcnn_select(N.ptr(out), n, C, float(thresh), N.ptr(box), N.ptr(img), N.ptr(obox),
+                                        N.ptr(oscore), N.ptr(oreg), N.ptr(oimg), N.ptr(opts), counter_ptr, N.ptr(ws),
+                                        nws, self._s()), "fr_mtcnn_select")
+        return obox, oscore, oreg, oimg, opts
+
+    def _detect_batch_device(self, imgs):
+        """detect_batch's device path: per image (boxes, points), or None when the P stage passed more
+        candidates than the capacity."""
+        import torch
+        L, dev, cap, th = N.lib(), self.device, self.capacity, self.thresholds
+        B, H, W, _ = imgs.shape
+        f32 = np.float32
+        empty = ([np.zeros((0, 5), f32) for _ in range(B)], [np.zeros((0, 5, 2), f32) for _ in range(B)])
+        scales = pyramid_scales(H, W, self.min_face_size, self.factor)
+        if not scales:
+            return empty
+        t0 = time.perf_counter()
+        box = torch.empty((cap, 4), dtype=torch.float32, device=dev)
+        score = torch.zeros((cap,), dtype=torch.float32, device=dev)
+        reg = torch.empty((cap, 4), dtype=torch.float32, device=dev)
+        seg = torch.zeros((cap,), dtype=torch.int32, device=dev)
+        counters = torch.zeros((8,), dtype=torch.int32, device=dev)  # P candidates, P crops, R select, R crops, O select
+        cptr = lambda k: N.ptr(counters) + 4 * k  # noqa: E731
+        full = torch.as_tensor(np.array([[b, 0, 0, H, W] for b in range(B)], np.int32)).to(dev)
+        for lvl, scale in enumerate(scales):
+            m = self.pnet(self._resample_dev(imgs, full, B, int(H * scale + 1), int(W * scale + 1)))
+            hh, ww = int(m.shape[1]), int(m.shape[2])
+            ws, nws = self._compact_ws(B * hh * ww)
+            N.check(L.fr_mtcnn_candidates(N.ptr(m), B, hh, ww, float(scale), float(th[0]), lvl, cap, N.ptr(box),
+                                          N.ptr(score), N.ptr(reg), N.ptr(seg), cptr(0), N.ptr(ws), nws, self._s()),
+                    "fr_mtcnn_candidates")
+        ar = torch.arange(cap, dtype=torch.int64, device=dev)
+        n_lb = len(scales) * B
+        keep1, sk1 = self._nms_dev(box, cap, score, seg, ar < counters[0].clamp(max=cap), None, n_lb, 0.5)
+        # the per-level survivors, level-major as detect_face concatenates them, then one segment per image
+        keep2, sk2 = self._nms_dev(box, cap, score[keep1], seg[keep1] % B, ar < sk1[n_lb], keep1, B, 0.7)
+        pbox, pscore, pimg, pregions = self._crop_boxes(box, score, reg, seg, cap, B, keep2, sk2, B, 0, W, H, cptr(1))
+        n_cand, n = (int(v) for v in counters[:2].cpu())  # readback 1: sizes the R stage
+        _cnt("readback_n", 1)
+        _cnt("pnet_pass_n", n_cand)
+        _acc("pnet_ms", t0, n)
+        if n_cand > cap:
+            return None
+        if n == 0:
+            return empty
+        # R stage
+        t0 = time.perf_counter()
+        out = self.rnet(self._resample_dev(imgs, pregions, n, 24, 24))
+        sbox, sscore, sreg, simg, _ = self._select(out, n, th[1], pbox, pimg, cptr(2))
+        keep3, sk3 = self._nms_dev(sbox, n, sscore, simg, ar[:n] < counters[2], None, B, 0.7)
+        rbox, rscore, rimg, rregions = self._crop_boxes(sbox, sscore, sreg, simg, n, B, keep3, sk3, B, 1, W, H, cptr(3))
+        n_prev, n = n, int(counters[3].cpu())  # readback 2: sizes the O stage
+        _cnt("readback_n", 1)
+        _acc("rnet_ms", t0, n_prev)
+        if n == 0:
+            return empty
+        # O stage
+        t0 = time.perf_counter()
+        out = self.onet(self._resample_dev(imgs, rregions, n, 48, 48))
+        obox, oscore, oreg, oimg, opts = self._select(out, n, th[2], rbox, rimg, cptr(4))
+        fbox = torch.empty((n, 4), dtype=torch.float32, device=dev)
+        fpts = torch.empty((n, 10), dtype=torch.float32, device=dev)
+        N.check(L.fr_mtcnn_final_boxes(N.ptr(obox), N.ptr(oreg), N.ptr(opts), n, cptr(4), N.ptr(fbox), N.ptr(fpts),
+                                       self._s()), "fr_mtcnn_final_boxes")
+        n_prev, n = n, int(counters[4].cpu())  # readback 3
+        _cnt("readback_n", 1)
+        _acc("onet_ms", t0, n_prev)
+        if n == 0:
+            return empty
+        rows = torch.cat([fbox[:n], oscore[:n, None], oimg[:n, None].to(torch.float32), fpts[:n]], 1).cpu().numpy()
+        _cnt("readback_n", 1)  # the results themselves
+        boxes, points = [], []
+        for b in range(B):
+            r = rows[rows[:, 5] == b]
+            bb, pp = np.ascontiguousarray(r[:, :5]), r[:, 6:16].reshape(-1, 5, 2)
+            # the last NMS is 'Min' mode in numpy's (unstable) argsort order: on the host, as detect_face's
+            pk = nms(bb, bb[:, 4], 0.7, "min")
+            boxes.append(bb[pk])
+            points.append(pp[pk])
+        _cnt("final_n", sum(len(b) for b in boxes))
+        return boxes, points
+
+    def detect_batch(self, frames_u8):
+        """detect_face for a batch of equal-size RGB u8 frames [B, H, W, 3] (numpy or device) with the box logic
+        on the device: per level resample -> P-net -> fr_mtcnn_candidates over the whole batch, one fr_nms over
+        the (level, image) segments and one over the per-image segments, then regression / squaring / padding /
+        crops, R-net and O-net with their selections, all from device buffers; one blocking readback per stage
+        sizes the next one, and the O-stage survivors come back in one copy for the host 'Min'-mode NMS.
+        Segments are per image (no coordinate offsets), so frame b gives bit for bit what
+        ``detect_face(frames[b][None])`` gives.  When the P stage passes more than ``capacity`` candidates the
+        call finishes through detect_face, frame by frame (STATS["device_fallback_n"]).  Returns what detect_face
+        returns: per frame boxes [n, 5] and points [n, 5, 2]."""
+        import torch
+        imgs = torch.as_tensor(frames_u8) if not torch.is_tensor(frames_u8) else frames_u8
+        if imgs.ndim != 4 or imgs.shape[-1] != 3 or imgs.dtype != torch.uint8:
+            raise ValueError(f"detect_batch takes RGB u8 frames [B, H, W, 3], got {tuple(imgs.shape)} {imgs.dtype}")
+        imgs = imgs.to(self.device).contiguous()
+        if imgs.shape[0] == 0:
+            return [], []
+        res = self._detect_batch_device(imgs)
+        if res is not None:
+            return res
+        _cnt("device_fallback_n", 1)
+        boxes, points = [], []
+        for b in range(imgs.shape[0]):
+            bb, pp = self.detect_face(imgs[b:b + 1])
+            boxes.append(bb[0])
+            points.append(pp[0])
+        return boxes, points
+
+    def _largest_first(self, box, point):
+        if self.select_largest:
+            order = np.argsort((box[:, 2] - box[:, 0]) * (box[:, 3] - box[:, 1]))[::-1]
+            box, point = box[order], point[order]
+        return box, point
+
     def detect(self, img_rgb_u8, landmarks: bool = True):
         """MTCNN.detect(img, landmarks=True) for one RGB u8 image [H, W, 3]: (boxes [n, 4] or None, probs,
         points [n, 5, 2]), the largest box first when select_largest."""
@@ -421,9 +605,7 @@ class DeviceMTCNN:
         box, point = boxes[0], points[0]
         if len(box) == 0:
             return (None, [None], None) if landmarks else (None, [None])
-        if self.select_largest:
-            order = np.argsort((box[:, 2] - box[:, 0]) * (box[:, 3] - box[:, 1]))[::-1]
-            box, point = box[order], point[order]
+        box, point = self._largest_first(box, point)
         return (box[:, :4], box[:, 4], point) if landmarks else (box[:, :4], box[:, 4])
 
 
@@ -461,10 +643,30 @@ class FaceDetector:
         rgb = np.ascontiguousarray(image[..., ::-1]) if image.ndim == 3 and image.shape[2] == 3 else image
         return self.detect_rgb(rgb)
 
+    def detect_batch(self, images: Sequence[np.ndarray]) -> List[Optional[Dict]]:
+        """detect() for a batch of equal-size BGR u8 frames ([B, H, W, 3] or a list of [H, W, 3]) through
+        DeviceMTCNN.detect_batch: one pass over the batch, the box logic on the device, detect_rgb's selection
+        rule per frame."""
+        frames = np.asarray(images)
+        if frames.ndim != 4 or frames.shape[-1] != 3 or frames.size == 0:
+            raise ValueError("detect_batch takes equal-size BGR frames [B, H, W, 3]")
+        boxes, points = self.detector.detect_batch(np.ascontiguousarray(frames[..., ::-1], dtype=np.uint8))
+        out = []
+        for box, point in zip(boxes, points):
+            if len(box) == 0:
+                out.append(None)
+                continue
+            box, point = self.detector._largest_first(box, point)
+            out.append(self._choose(box[:, :4], box[:, 4], point))
+        return out
+
     def detect_rgb(self, rgb: np.ndarray) -> Optional[Dict]:
         boxes, probs, landmarks = self.detector.detect(rgb, landmarks=True)
         if boxes is None or len(boxes) == 0:
             return None
+        return self._choose(boxes, probs, landmarks)
+
+    def _choose(self, boxes, probs, landmarks) -> Optional[Dict]:
         probs = np.asarray(probs)
         valid = probs >= self.confidence_threshold
         if not np.any(valid):

@@ -532,13 +532,43 @@ class RecognitionEngine:
         return self.recognize_batch([img_input], use_faiss, k)[0]
 
     def recognize_batch(self, img_inputs: List, use_faiss: bool = None, k: int = 5) -> List[Dict]:
+        return self._recognize_detected(img_inputs, None, use_faiss, k)
+
+    def recognize_frames(self, frames_bgr, use_faiss: bool = None, k: int = 5) -> List[Dict]:
+        """recognize() for a batch of equal-size BGR u8 frames ([B, H, W, 3] or a list of [H, W, 3]; a video
+        stream, the web app's batch page): one FaceDetector.detect_batch over the frames (the box logic on the
+        device), one align_faces launch over every chosen face, one embed, one match.  Returns the per-frame
+        dicts of recognize(); a frame without a face takes the path recognize() takes for it."""
+        import torch
+        from PIL import Image
+        from .align import align_faces
+        frames = np.asarray(frames_bgr)
+        if frames.ndim != 4 or frames.shape[-1] != 3 or frames.size == 0:
+            raise ValueError("recognize_frames takes equal-size BGR frames [B, H, W, 3]")
+        frames = np.ascontiguousarray(frames, dtype=np.uint8)
+        detected = [f for f in frames]
+        if self.use_face_detection and self.face_detector is not None and self.model is not None:
+            dets = self.face_detector.detect_batch(frames)
+            pick = [n for n, d in enumerate(dets) if d is not None and d.get("landmarks")]
+            if pick:
+                rgb = torch.as_tensor(np.ascontiguousarray(frames[pick][..., ::-1])).to(self.model.device)
+                crops, ok = align_faces(rgb, [dets[n]["landmarks"] for n in pick])
+                crops = crops.cpu().numpy()
+                for r, n in enumerate(pick):
+                    # all-zero landmarks are not aligned: that frame takes recognize()'s margin-crop path
+                    detected[n] = Image.fromarray(crops[r]) if ok[r] else self._detected(frames[n])
+        return self._recognize_detected(detected, detected, use_faiss, k)
+
+    def _recognize_detected(self, img_inputs: List, detected: Optional[List], use_faiss: bool, k: int) -> List[Dict]:
+        """recognize_batch's body; ``detected`` (optional) holds the image each embedding is taken from, in place of
+        ``_detected(img)``."""
         results = [{"identity": "Unknown", "confidence": 0.0, "top_k": [], "embedding": None, "status": "success"}
                    for _ in img_inputs]
         ok, crops = [], []
         if self.model is not None:
             for n, img in enumerate(img_inputs):
                 try:
-                    crops.append(_load_u8(self._detected(img), self.transform))
+                    crops.append(_load_u8(self._detected(img) if detected is None else detected[n], self.transform))
                     ok.append(n)
                 except Exception as e:
                     if isinstance(img, str):

@@ -306,6 +306,65 @@ int fr_mtcnn_head(const float* x, int64_t M, int C, const float* w, const float*
 int fr_nms_host(const float* boxes, int64_t n, const int64_t* order, float thresh, int min_mode, int64_t* keep,
                 int64_t* n_keep);
 
+/* Greedy NMS on the device (nms_device.hip): fr_nms_host's contract over independent segments, every buffer in device
+ * memory.  boxes [n][4] float32 (16-byte aligned); order [n] int64, the visiting order; seg_start [n_seg + 1] int64,
+ * a CSR that cuts order into segments (seg_start[0] <= ... <= seg_start[n_seg] <= n; entries of order past
+ * seg_start[n_seg] are never read); thresh and min_mode as fr_nms_host.  Segment s visits boxes
+ * order[seg_start[s] .. seg_start[s + 1]) and never sees another segment's boxes.  keep [n] int64 receives the kept
+ * box indices, segment after segment, each in greedy order; seg_kept [n_seg + 1] int64 is their CSR.  The kept
+ * lists equal fr_nms_host run on each segment with the same order, element for element (the same float32 operations
+ * in the same order, IEEE division; degenerate boxes included).  An order entry outside [0, n) is skipped.
+ * One workgroup per segment walks it in chunks of 64 candidates against the kept list: O(n x kept / 1024) per segment,
+ * n / 64 sequential steps; meant for the 10^2..10^4 boxes per segment of a working detector.
+ * ws: fr_nms_workspace(n, n_seg) bytes of device memory, 16-byte aligned (0 bytes are reported as an error: n or n_seg
+ * out of range).  n_seg == 0 returns at once; n == 0 zeroes seg_kept and launches nothing; a workgroup with an empty
+ * segment returns at once.  Refused with FR_ERR_ARG and a message before any HIP call: null or misaligned pointers,
+ * n < 0 or > 2^30, n_seg < 0 or > 2^24, a non-finite or negative thresh, min_mode not 0 / 1, a short workspace. */
+size_t fr_nms_workspace(int64_t n, int64_t n_seg);
+int fr_nms(const float* boxes, int64_t n, const int64_t* order, const int64_t* seg_start, int64_t n_seg, float thresh,
+           int min_mode, int64_t* keep, int64_t* seg_kept, void* ws, size_t ws_bytes, void* stream);
+
+/* ---- box stages of the batched detector (mtcnn_boxes.hip; DeviceMTCNN.detect_batch): detect_face's numpy lines
+ *      between the nets as launches over device buffers, float32 with every product rounded before its add,
+ *      bit-identical to the host path.  A selection keeps the input order through an ordered compaction (counts per
+ *      workgroup, an exclusive scan, writes behind an in-wave prefix; no atomics).  Boxes are [.][4] float32
+ *      (x1, y1, x2, y2) and regression rows [.][4] float32, both 16-byte aligned; scores [.] float32; image or
+ *      segment ids [.] int32; counters are device int32.  ws: fr_mtcnn_compact_workspace(items) bytes of device
+ *      memory (items = B hh ww, or n).  Every limit is FR_ERR_ARG with a message before any HIP call. ---- */
+size_t fr_mtcnn_compact_workspace(int64_t total);
+/* P-net candidates of one pyramid level: from map [B][hh][ww][6] (prob(bg), prob(face), reg x4) the cells with
+ * prob(face) >= thresh in np.nonzero order (image, y, x), appended behind the running total *counter (the previous
+ * level's call left it there; zero it before level 0): box = (floor((2 x + 1) / scale), floor((2 y + 1) / scale),
+ * floor((2 x + 12) / scale), floor((2 y + 12) / scale)), score = prob(face), reg = the four regression values,
+ * seg = level * B + image.  *counter += this level's count, also past capacity: rows at or past capacity are counted
+ * and not written.  B, hh, ww >= 1 with B hh ww <= 2^30, scale finite > 0, thresh finite >= 0, 0 <= level <= 4095,
+ * 1 <= capacity <= 2^30. */
+int fr_mtcnn_candidates(const float* map, int B, int hh, int ww, float scale, float thresh, int level,
+                        int64_t capacity, float* box, float* score, float* reg, int32_t* seg, int32_t* counter,
+                        void* ws, size_t ws_bytes, void* stream);
+/* R-net (C = 6) / O-net (C = 16) selection: the rows of out [n][C] with out[.][1] > thresh (strict), in row order:
+ * obox = box of the row, oscore = out[.][1], oreg = out[.][2..6), oimg = img of the row, and for C = 16
+ * opts [.][10] = out[.][6..16) (opts is NULL exactly when C = 6).  *counter = the number of rows kept.  Outputs
+ * hold n rows.  1 <= n <= 2^30, thresh finite >= 0. */
+int fr_mtcnn_select(const float* out, int64_t n, int C, float thresh, const float* box, const int32_t* img,
+                    float* obox, float* oscore, float* oreg, int32_t* oimg, float* opts, int32_t* counter, void* ws,
+                    size_t ws_bytes, void* stream);
+/* Regression, _rerec, _pad and the ok filter, one thread per box.  Row i takes source row g = keep[i] (keep NULL:
+ * g = i) for i < *n_keep (n_keep NULL: i < n; both device int64, as fr_nms leaves them); n is the number of source
+ * rows and the bound on i.  plus1 = 0 is the P stage's b + reg (x2 - x1), plus1 = 1 is _bbreg's
+ * b + reg (x2 - x1 + 1); then _rerec ((b + w 0.5) - l 0.5, then + l), _pad (truncate to int32, clamp to 1 / W / H)
+ * and ok = (ey > y - 1) & (ex > x - 1).  The rows that pass ok, in order: obox = the squared box, oscore = score[g],
+ * oimg = img[g] % B, regions [.][5] int32 = (image, y - 1, x - 1, ey - y + 1, ex - x + 1), fr_area_resample_u8's
+ * layout.  *counter = their number.  Outputs hold n rows. */
+int fr_mtcnn_crop_boxes(const float* box, const float* score, const float* reg, const int32_t* img, int64_t n, int B,
+                        const int64_t* keep, const int64_t* n_keep, int plus1, int W, int H, float* obox,
+                        float* oscore, int32_t* oimg, int32_t* regions, int32_t* counter, void* ws, size_t ws_bytes,
+                        void* stream);
+/* The O stage's last lines for rows i < min(n, *n_dev) (n_dev NULL: n): opts [.][5][2] = the landmark points
+ * ((w pt) + x1) - 1, ((h pt) + y1) - 1 from pts [.][10] (five x then five y), w = x2 - x1 + 1, and obox = _bbreg. */
+int fr_mtcnn_final_boxes(const float* box, const float* reg, const float* pts, int64_t n, const int32_t* n_dev,
+                         float* obox, float* opts, void* stream);
+
 /* ---- LBPH (the models/lbphmodel package, cv2.face.LBPHFaceRecognizer): OpenCV's published algorithm restated, handle-free.
  *      Checked against a float32/float64 numpy restatement (tests/lbph_ref.py), not against a cv2.face build.
  *      A histogram is kept as u16 counts [D], D = grid_x * grid_y * 2^neighbors, cells row-major; OpenCV's float32
