@@ -655,12 +655,6 @@ void head_plan(int M, int Cout, int Kpad, int* tile, int* split) {
 }
 
 hipError_t launch_conv(const ConvArgs& a, hipStream_t s) {
-    if (a.tile == TILE_WRING) {  // conv_wring.hip (an autotuner pick)
-        ConvArgs w = a;
-        w.wimg = a.wring_;
-        return launch_conv_wring(w, s);
-    }
-    if (a.tile == TILE_DIRECT) return launch_conv_direct(a, 0, s);  // conv_direct.hip (an autotuner pick)
     return a.f16 ? launch_dtype<true>(a, s) : launch_dtype<false>(a, s);
 }
 

@@ -1,6 +1,7 @@
 // frhip engine: C-ABI handle, weight-blob loader, static per-arch forward plans and the
 // gallery/match entry points.  See include/frhip.h for the boundary contract and
-// DESIGN.md for the data layout.  The fused stages of a plan (their kinds, packers, launches) are in stages.cpp.
+// DESIGN.md for the data layout.  The fused stages of a plan (their kinds, packers, launches) are in stages.cpp,
+// how a conv gets its kernel (the conv kernel kinds, the tuner, the op API's forced kernels) in convs.cpp.
 //
 // The forward plans restate the reference backbones as a list of fused ops:
 //   FR_ARCH_RESNET50_ARCFACE  models/arcface/arcface_model.py:118-132 + head :192-196
@@ -95,7 +96,6 @@ struct HostT {
 int round_up(int x, int m) { return (x + m - 1) / m * m; }
 
 constexpr size_t FR_MAX_SPLIT_STAGES = 6;  // stage ops per plan (at most one per residual layer + the transition)
-constexpr int FR_SPLITK_TILES = 1 << 16;   // in-launch split-K tile counters per handle
 
 void drop_graphs(fr_handle* h) {
     if (h->graphs.empty()) return;
@@ -609,79 +609,6 @@ void build_iresnet100(Builder& b) {
     b.head(x);
 }
 
-// K-step slice images for the convs the conv_img.hip kernels apply to (3x3/s1/p1 28x28x128 and
-// 56x56x64), packed on the device from the uploaded [Npad][Kpad] rows.
-int build_img_weights(fr_handle* h) {
-    for (const auto& op : h->ops) {
-        if (op.kind != OP_CONV || op.wi < 0) continue;
-        DevConvW& cw = h->convw[op.wi];
-        if ((cw.wimg || cw.wrows) && cw.wring) continue;
-        ConvArgs a{};
-        a.B = 1; a.Cin = op.cin; a.Kh = op.kh; a.Kw = op.kw; a.sh = op.sh; a.sw = op.sw; a.ph = op.ph; a.pw = op.pw;
-        a.H = h->tensors[op.in].H; a.W = h->tensors[op.in].W; a.Cx = h->tensors[op.in].C; a.x_off = op.in_off;
-        a.Ho = h->tensors[op.out].H; a.Wo = h->tensors[op.out].W; a.Cy = h->tensors[op.out].C; a.y_off = op.out_off;
-        a.Cout = cw.Cout; a.Npad = cw.Npad; a.Kpad = cw.Kpad; a.bias9 = cw.bias9;
-        a.y2 = op.out2 >= 0 ? (bf16_t*)1 : nullptr;
-        if (op.res >= 0) { a.res = (const bf16_t*)1; a.Cres = h->tensors[op.res].C; a.res_off = op.res_off; }
-        a.f16 = h->dtype == FR_DTYPE_F16;
-        int ic = 0;
-        if (cw.w8) continue;  // e4m3 convs: conv_fp8.hip or the fp8 stage only
-        if (!cw.wring) {  // conv_wring.hip substep images (the autotuner decides per shape whether they run)
-            ConvArgs w = a;
-            w.K = cw.K;
-            w.x2 = nullptr;
-            if (op.x2 >= 0) { w.x2 = (const bf16_t*)1; w.C2 = cw.C2; w.K1 = cw.K1; }
-            if (wring_supported(w)) {
-                void* q = nullptr;
-                int rc = dev_alloc(&q, wring_packed_elems(cw.Kpad, cw.Npad) * sizeof(bf16_t));
-                if (rc) return rc;
-                h->weight_allocs.push_back(q);
-                FR_HIP_CHECK(wring_pack_weights(cw.w, cw.Kpad, cw.Npad, (bf16_t*)q, nullptr));
-                cw.wring = (bf16_t*)q;
-            }
-        }
-        // the activation's negative-side factor (conv_img and conv_rows epilogues)
-        auto make_negf = [&]() -> int {
-            if (cw.negf) return FR_OK;
-            std::vector<float> nf(cw.Npad, op.act == 1 ? 0.f : 1.f);
-            if (op.act == 2 && cw.slope)
-                FR_HIP_CHECK(hipMemcpy(nf.data(), cw.slope, cw.Cout * sizeof(float), hipMemcpyDeviceToHost));
-            return upload(h, &cw.negf, nf);
-        };
-        {
-            ConvArgs r = a;
-            r.wimg = (const bf16_t*)1;
-            if (rows_supported(r) && !cw.wrows) {
-                void* q = nullptr;
-                int rc = dev_alloc(&q, rows_packed_elems(cw.Cout) * sizeof(bf16_t));
-                if (rc) return rc;
-                h->weight_allocs.push_back(q);
-                FR_HIP_CHECK(rows_pack_weights(cw.w, cw.Kpad, cw.Cout, (bf16_t*)q, nullptr));
-                cw.wrows = (bf16_t*)q;
-                std::vector<float> ep((size_t)9 * cw.Npad, 0.f);
-                if (cw.bias9) {
-                    FR_HIP_CHECK(hipMemcpy(ep.data(), cw.bias9, ep.size() * sizeof(float), hipMemcpyDeviceToHost));
-                } else if (cw.bias) {
-                    FR_HIP_CHECK(hipMemcpy(ep.data(), cw.bias, cw.Npad * sizeof(float), hipMemcpyDeviceToHost));
-                    for (int k = 1; k < 9; ++k) std::copy(ep.begin(), ep.begin() + cw.Npad, ep.begin() + k * cw.Npad);
-                }
-                if ((rc = upload(h, &cw.ep, ep))) return rc;
-                if ((rc = make_negf())) return rc;
-            }
-        }
-        if (cw.wimg || !img_shape_ok(a, &ic)) continue;
-        void* p = nullptr;
-        int rc = dev_alloc(&p, img_packed_elems(ic) * sizeof(bf16_t));
-        if (rc) return rc;
-        h->weight_allocs.push_back(p);
-        FR_HIP_CHECK(img_pack_weights(cw.w, cw.Kpad, ic, (bf16_t*)p, nullptr));
-        cw.wimg = (bf16_t*)p;
-        if ((rc = make_negf())) return rc;
-    }
-    FR_HIP_CHECK(hipDeviceSynchronize());
-    return FR_OK;
-}
-
 void build_resnet50(Builder& b) {
     fr_handle* h = b.h;
     h->in_size = 112;
@@ -1044,352 +971,9 @@ int reserve(fr_handle* h, int maxB) {
     return fill_stage_dbg(h);
 }
 
-// layer2 band kernel (conv_img.hip): 80 us per conv vs 86 us for the implicit GEMM
-// (profiles/r01_img28.txt); FR_AB no_img28 falls back to the implicit GEMM
-bool img28_enabled() {
-    static const bool on = [] { return !ab_int("no_img28", 0); }();
-    return on;
-}
-
-bool rows_enabled() {
-    static const bool on = [] { return !ab_int("no_rows", 0); }();
-    return on;
-}
-
-bool img56_enabled() {
-    static const bool on = [] { return ab_int("img56", 0) != 0; }();
-    return on;
-}
-
 bool stem_fuse_enabled() {
     static const bool on = [] { return !ab_int("no_stem_fuse", 0); }();
     return on;
-}
-
-bool band_enabled() {
-    static const bool on = [] { return !ab_int("no_band", 0); }();
-    return on;
-}
-
-double conv_flops(const ConvArgs& a) { return 2.0 * (double)a.M * a.Cout * ((double)a.Cin * a.Kh * a.Kw + (a.x2 ? a.C2 : 0)); }
-
-// Algorithmic HBM bytes of a conv launch: its input channels once (all input pixels), the projection
-// input at the output's stride, the residual, the output and the weights once (activations 2 B; fp8
-// weights 1 B).  Re-reads through L2 / MALL are not counted: this is the roofline's traffic floor.
-double conv_bytes(const ConvArgs& a) {
-    const double act = 2.0;
-    double b = (double)a.B * a.H * a.W * a.Cin * act;
-    if (a.x2) b += (double)a.M * a.C2 * act;
-    if (a.res) b += (double)a.M * a.Cout * act;
-    b += (double)a.M * a.Cout * act * (a.y2 ? 2.0 : 1.0);
-    b += (double)a.Cout * ((double)a.Cin * a.Kh * a.Kw + (a.x2 ? a.C2 : 0)) * (a.w8 ? 1.0 : 2.0);
-    return b;
-}
-
-bool autotune_enabled() {
-    static const bool on = [] { return ab_int("autotune", 1) != 0; }();
-    return on;
-}
-
-void shape_key(const ConvArgs& a, int* k) {
-    const int v[13] = {a.M, a.Cout, a.Kpad, a.Cin, a.Kh, a.Kw, a.sh, a.sw, a.res ? 1 : 0, a.y2 ? 1 : 0, a.H, a.W, a.x2 ? 1 : 0};
-    for (int i = 0; i < 13; ++i) k[i] = v[i];
-}
-
-// A conv's kernel: an FR_TILE_* id (the implicit-GEMM tiles, or one of the specialised kernels: row bands,
-// image bands, weight-resident rows, register weight ring, small-K direct) and a split-K factor (tiles only).
-struct ConvChoice {
-    int tile = -1, split = 1;
-};
-
-static bool find_tuned(const fr_handle* h, const ConvArgs& a, ConvChoice* c) {
-    int k[13];
-    shape_key(a, k);
-    for (const auto& t : h->tuned)
-        if (std::memcmp(t.key, k, sizeof(k)) == 0) {
-            c->tile = t.tile;
-            c->split = t.split;
-            return true;
-        }
-    return false;
-}
-
-static bool wring_enabled() {
-    static const bool on = [] { return !ab_int("no_wring", 0); }();
-    return on;
-}
-
-static bool direct_enabled() {
-    static const bool on = [] { return !ab_int("no_direct", 0); }();
-    return on;
-}
-
-static bool rows_ok(const ConvArgs& a) {
-    if (!rows_enabled() || !a.wrows_ || !a.ep || !a.negf) return false;
-    ConvArgs r = a;
-    r.wimg = a.wrows_;
-    return rows_supported(r);
-}
-
-static bool band_ok(const ConvArgs& a) {
-    int TH, variant;
-    return band_enabled() && !a.y_amax && band_plan(a, &TH, &variant) && variant >= 3;
-}
-
-// the split-K factor the partial workspace allows (reserve() sizes it for conv_plan's splits)
-static int fit_split(const fr_handle* h, const ConvArgs& a, int split) {
-    while (split > 1 && (size_t)split * a.M * a.Npad > h->partial_floats) split /= 2;
-    return split;
-}
-
-// The fixed policy (no measurement: FR_AB autotune=0, a forced FR_AB conv_tile): the specialised kernels where they
-// apply (each measured faster than the implicit GEMM at bs = 256), else conv_plan's cost-model tile and split.
-
-static ConvChoice default_choice(const fr_handle* h, const ConvArgs& a) {
-    ConvChoice c;
-    if (h->invariant) {  // the cost model's tile, unsplit (every igemm tile sums K in the same order)
-        conv_plan(a.M, a.Cout, a.Kpad, &c.tile, &c.split);
-        c.split = 1;
-        return c;
-    }
-    if (rows_ok(a)) { c.tile = FR_TILE_ROWS; return c; }
-    if (img28_enabled() && img28_supported(a)) { c.tile = FR_TILE_IMG28; return c; }
-    if (img56_enabled() && img56_supported(a)) { c.tile = FR_TILE_IMG56; return c; }
-    if (band_ok(a)) { c.tile = FR_TILE_BAND; return c; }
-    conv_plan(a.M, a.Cout, a.Kpad, &c.tile, &c.split);
-    c.split = fit_split(h, a, c.split);
-    return c;
-}
-
-// Launches choice c (no timing scope; run_conv_args adds it).
-static hipError_t launch_choice(fr_handle* h, ConvArgs& a, const ConvChoice& c, hipStream_t s) {
-    a.split_k = 1;
-    a.partial = nullptr;
-    switch (c.tile) {
-        case FR_TILE_SMALL: return launch_conv_small(a, c.split, s);
-        case FR_TILE_ROWS: {
-            ConvArgs r = a;
-            r.wimg = a.wrows_;
-            return launch_conv_rows(r, h->n_cu, s);
-        }
-        case FR_TILE_IMG28: return launch_conv_img28(a, s);
-        case FR_TILE_IMG56: return launch_conv_img56(a, s);
-        case FR_TILE_BAND: {
-            int TH, variant;
-            if (!band_plan(a, &TH, &variant)) return hipErrorInvalidValue;
-            return launch_conv_band(a, TH, variant, s);
-        }
-        default: break;
-    }
-    a.tile = c.tile;
-    a.splitk_cnt = nullptr;
-    const int split = c.split < 0 ? -c.split : c.split;  // negative: reduced in-launch
-    if (split > 1) {
-        a.split_k = split;
-        a.partial = h->partial;
-        // in-launch: the last of each tile's split workgroups reduces (conv_igemm.hip), where the tile counters
-        // fit; else the separate split-K epilogue launch
-        const int64_t tiles = (int64_t)((a.M + conv_tile_bm(c.tile) - 1) / conv_tile_bm(c.tile)) *
-                              ((a.Cout + conv_tile_bn(c.tile) - 1) / conv_tile_bn(c.tile));
-        // (the in-launch slabs are addressed by 32-bit buffer offsets)
-        if (c.split < 0 && a.y && h->splitk_cnt && tiles <= FR_SPLITK_TILES && h->splitk_inlaunch &&
-            (size_t)split * a.M * a.Npad * sizeof(float) < 0x7fffffffull) {
-            a.splitk_cnt = h->splitk_cnt;
-            h->inlaunch_used = true;
-        }
-    }
-    hipError_t e = launch_conv(a, s);
-    if (e == hipSuccess && split > 1 && a.y && !a.splitk_cnt) e = launch_splitk_epilogue(a, s);
-    return e;
-}
-
-static std::string choice_class(const ConvArgs& a, const ConvChoice& c) {
-    switch (c.tile) {
-        case FR_TILE_ROWS: return "conv3x3_rows W" + std::to_string(a.W) + " N" + std::to_string(a.Cout);
-        case FR_TILE_IMG28: return "conv3x3_img W28";
-        case FR_TILE_IMG56: return "conv3x3_img W56";
-        case FR_TILE_BAND: {
-            int TH = 0, variant = 0;
-            band_plan(a, &TH, &variant);
-            return "conv3x3_band W" + std::to_string(a.W) + " v" + std::to_string(variant);
-        }
-        case FR_TILE_WRING: return "conv_wring";
-        case FR_TILE_DIRECT: return "conv_direct";
-        case FR_TILE_SMALL: return "conv_small";
-        default:
-            return "conv_igemm tile" + std::to_string(c.tile) + (c.split > 1 ? " splitk" : c.split < -1 ? " splitk-inlaunch" : "");
-    }
-}
-
-// Time every applicable kernel on this conv (1 warm + 3 timed launches each, three interleaved passes, the
-// best time per candidate, HIP events on `s`) and remember the fastest for the shape.  Candidates: the
-// specialised kernels that apply, every implicit-GEMM tile unsplit, the register-weight-ring and small-K
-// direct kernels, and conv_plan's split-K plan when it splits (small M: a few tiles over a long K).  Runs
-// only inside the eager tuning pass of embed_locked, so a batch size's choice is measured at that size
-// (bs = 1 and bs = 256 pick differently).  Every candidate sums K in the same order except split-K, whose
-// partial sums differ in f32 rounding only.
-int tune_conv(fr_handle* h, ConvArgs a, hipStream_t s) {
-    std::vector<ConvChoice> cand;
-    auto add = [&](int tile, int split) {
-        ConvChoice c;
-        c.tile = tile;
-        c.split = split;
-        cand.push_back(c);
-    };
-    const bool inv = h->invariant;  // only the kernels that sum K in the implicit GEMM's order (tile 0's bits)
-    if (!inv && rows_ok(a)) add(FR_TILE_ROWS, 1);
-    if (!inv && img28_enabled() && img28_supported(a)) add(FR_TILE_IMG28, 1);
-    if (!inv && img56_enabled() && img56_supported(a)) add(FR_TILE_IMG56, 1);
-    if (!inv && band_ok(a)) add(FR_TILE_BAND, 1);
-    int tiles[16];
-    const int nt = conv_tile_candidates(a.Cout, tiles);
-    for (int i = 0; i < nt; ++i) add(tiles[i], 1);
-    if (wring_enabled() && a.wring_) {  // the register-weight-ring kernel competes per shape
-        ConvArgs w = a;
-        w.wimg = a.wring_;
-        w.partial = nullptr;
-        if (wring_supported(w)) add(TILE_WRING, 1);
-    }
-    if (direct_enabled() && direct_supported(a)) add(TILE_DIRECT, 1);  // small-K direct conv
-    // small M (a few hundred pixels: small batches): one wave per 16 px x 64 ch, no LDS, no second launch
-    // (split 4 / 8: that many waves share a tile's K, summed through LDS)
-    // FR_AB small_nf4: only the 64-channel tiles (A/B)
-    static const bool small_nf4 = [] { return ab_int("small_nf4", 0) != 0; }();
-    if (a.M <= 8192)
-        for (int sp : {1, 4, 8, 4 | 2 << 8, 8 | 2 << 8, 4 | 1 << 8, 8 | 1 << 8, 16 | 1 << 8})
-            if ((!small_nf4 || sp < 256) && (!inv || (sp & 255) == 1) && small_supported(a, (sp >> 8) ? (sp >> 8) : 4))
-                add(FR_TILE_SMALL, sp);
-    // one wave per 16 px x 32 / 16 channels at any M: narrow-N convs (FaceNet Block35's N = 32 / 96) waste half of
-    // every implicit-GEMM tile
-    if (!small_nf4 && a.Cout <= 96)
-        for (int sp : {1 | 2 << 8, 1 | 1 << 8})
-            if (small_supported(a, sp >> 8)) add(FR_TILE_SMALL, sp);
-    {
-        int tile, split;
-        conv_plan(a.M, a.Cout, a.Kpad, &tile, &split);
-        split = fit_split(h, a, split);
-        if (split > 1 && !inv) {
-            add(tile, split);
-            if (h->splitk_inlaunch) add(tile, -split);  // the same split reduced in-launch (negative split)
-        }
-    }
-    hipEvent_t e0, e1;
-    FR_HIP_CHECK(hipEventCreate(&e0));
-    FR_HIP_CHECK(hipEventCreate(&e1));
-    // three interleaved passes, best time per candidate: one pass in candidate order let clock ramps
-    // and neighbours' cache state pick different tiles from run to run (profiles/r01_bench_runs.jsonl)
-    std::vector<float> cand_ms(cand.size(), 1e30f);
-    for (int pass = 0; pass < 3; ++pass) {
-        for (size_t c = 0; c < cand.size(); ++c) {
-            if (cand_ms[c] < 0.f) continue;  // failed to launch (a library candidate without an algorithm)
-            if (launch_choice(h, a, cand[c], s) != hipSuccess) {
-                (void)hipGetLastError();
-                cand_ms[c] = -1.f;
-                continue;
-            }
-            FR_HIP_CHECK(hipEventRecord(e0, s));
-            for (int r = 0; r < 3; ++r) FR_HIP_CHECK(launch_choice(h, a, cand[c], s));
-            FR_HIP_CHECK(hipEventRecord(e1, s));
-            FR_HIP_CHECK(hipEventSynchronize(e1));
-            float ms = 0.f;
-            FR_HIP_CHECK(hipEventElapsedTime(&ms, e0, e1));
-            cand_ms[c] = std::min(cand_ms[c], ms);
-        }
-    }
-    // the 3-stage implicit-GEMM tiles are credited FR_AB tune_s3_bias percent (default 5): the tuner's
-    // back-to-back launches run warm, where the deeper ring's latency hiding does not show, and in the
-    // forward they win (IRV1 Block17 1x7: 12.0 vs 17.4 us per launch for 11.5 vs 11.5 us tuned)
-    static const float s3_credit = 1.f - 0.01f * (float)ab_int("tune_s3_bias", 5);  // (the 64x64 3-stage tile too)
-    for (size_t c = 0; c < cand.size(); ++c)
-        if (cand_ms[c] >= 0.f && (cand[c].tile == TILE_128x64_S3 || cand[c].tile == TILE_64x128_S3 || cand[c].tile == TILE_64x64_S3 ||
-                                  cand[c].tile == TILE_32x64_S3) &&
-            cand[c].split == 1)
-            cand_ms[c] *= s3_credit;
-    size_t best = 0;
-    while (best + 1 < cand.size() && cand_ms[best] < 0.f) ++best;
-    for (size_t c = best + 1; c < cand.size(); ++c)
-        if (cand_ms[c] >= 0.f && cand_ms[c] < cand_ms[best] * 0.99f) best = c;
-    static const bool tune_log = ab_int("tune_log", 0) != 0;  // FR_AB tune_log=1: candidate times to stderr
-    if (tune_log) {
-        fprintf(stderr, "tune M=%d N=%d K=%d %dx%d:", a.M, a.Cout, a.Kpad, a.Kh, a.Kw);
-        for (size_t c = 0; c < cand.size(); ++c)
-            fprintf(stderr, " %d/%d=%.1f%s", cand[c].tile, cand[c].split, cand_ms[c] * 1000.f / 3.f, c == best ? "*" : "");
-        fprintf(stderr, "\n");
-    }
-    (void)hipEventDestroy(e0);
-    (void)hipEventDestroy(e1);
-    fr_handle::Tuned t;
-    shape_key(a, t.key);
-    t.tile = cand[best].tile;
-    t.split = cand[best].split;
-    h->tuned.push_back(t);
-    return FR_OK;
-}
-
-// The kernel choice of a conv launch: the measured one for its shape (tuned in the eager tuning forward of
-// the batch size), else the fixed policy; then the launch inside its timing scope.
-static bool choice_ok(const ConvArgs& a, const ConvChoice& c) {
-    switch (c.tile) {
-        case FR_TILE_ROWS: return rows_ok(a);
-        case FR_TILE_IMG28: return img28_enabled() && img28_supported(a);
-        case FR_TILE_IMG56: return img56_enabled() && img56_supported(a);
-        case FR_TILE_BAND: return band_ok(a);
-        case FR_TILE_WRING: {
-            ConvArgs w = a;
-            w.wimg = a.wring_;
-            w.partial = nullptr;
-            return a.wring_ && wring_supported(w);
-        }
-        case FR_TILE_DIRECT: return direct_supported(a);
-        case FR_TILE_SMALL: return small_split_ok(c.split) && small_supported(a, (c.split >> 8) ? (c.split >> 8) : 4);
-        default: return c.tile >= 0;
-    }
-}
-
-static bool invariant_ok(const ConvChoice& c) {
-    switch (c.tile) {
-        case FR_TILE_ROWS: case FR_TILE_IMG28: case FR_TILE_IMG56: case FR_TILE_BAND: return false;
-        case FR_TILE_SMALL: return (c.split & 255) == 1;
-        case FR_TILE_WRING: case FR_TILE_DIRECT: return true;
-        default: return c.split == 1;
-    }
-}
-
-static ConvChoice conv_choice(const fr_handle* h, const ConvArgs& a) {
-    ConvChoice c;
-    if (autotune_enabled() && !conv_tile_forced() && find_tuned(h, a, &c) && choice_ok(a, c) &&
-        (!h->invariant || invariant_ok(c)))
-        return c;
-    return default_choice(h, a);
-}
-
-int run_conv_args(fr_handle* h, ConvArgs& a, hipStream_t s) {
-    ProfScope ps(h, s);
-    ps.flops = conv_flops(a);
-    ps.bytes = conv_bytes(a);
-    if (a.w8) {  // FR_DTYPE_FP8 conv (conv_fp8.hip)
-        a.tile = conv_fp8_tile(a.M, a.Cout);
-        a.split_k = 1;
-        ps.start("conv_fp8 tile" + std::to_string(a.tile), &a);
-        FR_HIP_CHECK(launch_conv_fp8(a, s));
-        return FR_OK;
-    }
-    ConvChoice c;
-    if (autotune_enabled() && !conv_tile_forced() && !find_tuned(h, a, &c) && h->tuning) {
-        const int rc = tune_conv(h, a, s);
-        if (rc) return rc;
-    }
-    c = conv_choice(h, a);
-    if (c.tile == FR_TILE_ROWS) {  // the event pair rides on the launched args
-        ConvArgs r = a;
-        r.wimg = a.wrows_;
-        ps.start(choice_class(a, c), &r);
-        FR_HIP_CHECK(launch_conv_rows(r, h->n_cu, s));
-        return FR_OK;
-    }
-    ps.start(choice_class(a, c), &a);
-    FR_HIP_CHECK(launch_choice(h, a, c, s));
-    return FR_OK;
 }
 
 // Co-residency of a split stage's parts holds while the stage kernel is the only long-running kernel
@@ -1494,46 +1078,6 @@ int fr::run_maxpool_op(fr_handle* h, const Op& op, int B, int f16, hipStream_t s
     FR_HIP_CHECK(launch_maxpool(ti.dev, B, ti.H, ti.W, ti.C, 0, ti.C, op.pk, op.ps, op.pp, to.dev, to.C, op.out_off, to.H,
                                 to.W, f16 || ti.f16, s, ti.f16 && !to.f16 ? 1 : 0));
     return FR_OK;
-}
-
-// One conv op: its ConvArgs from the plan's tensors and weights, then the kernel choice (run_conv_args).
-int fr::run_conv_op(fr_handle* h, const Op& op, int B, int f16, hipStream_t s) {
-    const auto& cw = h->convw[op.wi];
-    const auto& ti = h->tensors[op.in];
-    const auto& to = h->tensors[op.out];
-    ConvArgs a{};
-    a.f16 = f16 || ti.f16;
-    a.y_bf16 = ti.f16 && !to.f16;  // f16 section -> bf16 plan boundary
-    a.x = ti.dev; a.B = B; a.H = ti.H; a.W = ti.W; a.Cx = ti.C; a.x_off = op.in_off; a.Cin = op.cin;
-    a.w = cw.w; a.Kh = op.kh; a.Kw = op.kw; a.sh = op.sh; a.sw = op.sw; a.ph = op.ph; a.pw = op.pw;
-    a.K = cw.K; a.Kpad = cw.Kpad;
-    a.Ho = to.H; a.Wo = to.W; a.M = B * to.H * to.W; a.Cout = cw.Cout; a.Npad = cw.Npad;
-    a.bias = cw.bias; a.slope = cw.slope; a.act = op.act; a.bias9 = cw.bias9; a.wimg = cw.wimg;
-    a.negf = cw.negf; a.ep = cw.ep;
-    a.wrows_ = cw.wrows;
-    a.wring_ = cw.wring;
-    if (op.res >= 0) { a.res = h->tensors[op.res].dev; a.Cres = h->tensors[op.res].C; a.res_off = op.res_off; }
-    if (op.x2 >= 0) {
-        const auto& t2 = h->tensors[op.x2];
-        a.x2 = t2.dev; a.H2 = t2.H; a.W2 = t2.W; a.Cx2 = t2.C; a.x2_off = op.x2_off;
-        a.C2 = cw.C2; a.st2 = op.st2; a.K1 = cw.K1;
-    }
-    a.y = to.dev; a.Cy = to.C; a.y_off = op.out_off;
-    if (op.out2 >= 0) {
-        a.y2 = h->tensors[op.out2].dev; a.Cy2 = h->tensors[op.out2].C; a.y2_off = 0;
-        a.aff_s = cw.aff_s; a.aff_b = cw.aff_b;
-    }
-    if (h->amax && h->need_amax[op.out]) {
-        a.y_amax = h->amax + (size_t)op.out * FR_AMAX_SLOTS;
-        a.amax_slots = FR_AMAX_SLOTS;
-    }
-    if (h->amax && cw.w8 && op.in_off == 0) {
-        a.w8 = cw.w8; a.wscale = cw.wscale; a.Kpad = cw.Kpad8;
-        a.x_amax = h->amax + (size_t)op.in * FR_AMAX_SLOTS;
-        a.amax_slots = FR_AMAX_SLOTS;  // every producer spreads its maxima over all the slots (read
-                                       // them all, also when this conv records no amax itself)
-    }
-    return run_conv_args(h, a, s);
 }
 
 namespace {
@@ -1823,7 +1367,7 @@ int fr_load_weights(fr_handle* h, const void* blob, size_t nbytes) {
     if (h->arch == FR_ARCH_IRESNET100) build_iresnet100(b);
     else if (h->arch == FR_ARCH_RESNET50_ARCFACE) build_resnet50(b);
     else build_irv1(b);
-    if (!b.rc) b.rc = build_img_weights(h);
+    if (!b.rc) b.rc = pack_conv_weights(h);
     for (auto& op : h->ops) op.grp = op.stage;  // plan entries (stage_plan)
     // the tensors whose producers record amax: inputs of e4m3 convs that run per-conv (an fp8 stage
     // scales its own input; its member convs are its fallback when the stage does not run)
@@ -2507,33 +2051,7 @@ int fr_debug_plan(fr_handle* h, int B, char* buf, size_t n) {
             out += std::string(op.kind == OP_PRE ? "pre" : op.kind == OP_MAXPOOL ? "maxpool" : "avgpool") + "\n";
             continue;
         }
-        const auto& cw = h->convw[op.wi];
-        const int M = op.kind == OP_HEAD ? B : B * h->tensors[op.out].H * h->tensors[op.out].W;
-        int tile, sp;
-        if (op.kind == OP_HEAD) head_plan(M, cw.Cout, cw.Kpad, &tile, &sp);
-        else conv_plan(M, cw.Cout, cw.Kpad, &tile, &sp);
-        if (op.kind == OP_CONV) {
-            ConvArgs a{};
-            a.M = M; a.Cout = cw.Cout; a.Kpad = cw.Kpad; a.Cin = op.cin; a.Kh = op.kh; a.Kw = op.kw;
-            a.sh = op.sh; a.sw = op.sw; a.H = h->tensors[op.in].H; a.W = h->tensors[op.in].W;
-            a.Ho = h->tensors[op.out].H; a.Wo = h->tensors[op.out].W; a.ph = op.ph; a.pw = op.pw;
-            a.res = op.res >= 0 ? (const bf16_t*)1 : nullptr;
-            a.y2 = op.out2 >= 0 ? (bf16_t*)1 : nullptr;
-            a.Npad = cw.Npad; a.B = B; a.wimg = cw.wimg; a.f16 = h->dtype == FR_DTYPE_F16; a.bias9 = cw.bias9;
-            a.Cx = h->tensors[op.in].C; a.x_off = op.in_off; a.Cy = h->tensors[op.out].C; a.y_off = op.out_off;
-            if (op.res >= 0) { a.Cres = h->tensors[op.res].C; a.res_off = op.res_off; }
-            a.wrows_ = cw.wrows; a.wring_ = cw.wring; a.ep = cw.ep; a.negf = cw.negf; a.K = cw.K;
-            if (op.x2 >= 0) { a.x2 = (const bf16_t*)1; a.C2 = cw.C2; a.K1 = cw.K1; a.st2 = op.st2; }
-            if (h->amax && h->need_amax[op.out]) a.y_amax = (float*)1;
-            const ConvChoice c = conv_choice(h, a);  // the measured kernel (after a forward at B), else the policy
-            tile = c.tile;
-            sp = c.split;
-        }
-        const std::string nm = op.kind == OP_HEAD ? "head" : h->tensors[op.out].name;
-        out += (op.kind == OP_HEAD ? "head " : "conv ") + std::to_string(M) + " " + std::to_string(cw.Cout) + " " +
-               std::to_string(cw.K) + " " + std::to_string(cw.Kpad) + " " + std::to_string(tile) + " " +
-               std::to_string(sp) + " " + std::to_string(op.kh) + "x" + std::to_string(op.kw) + " " +
-               (nm.empty() ? "-" : nm) + "\n";
+        out += conv_plan_line(h, op, B);
     }
     std::snprintf(buf, n, "%s", out.c_str());
     return out.size() + 1 <= n ? FR_OK : FR_ERR_ARG;
@@ -2802,13 +2320,6 @@ int fr_debug_copy_tensor(fr_handle* h, int t, int B, void* dst, void* stream) {
 
 int fr_op_conv2d(const fr_conv_desc* d, void* stream) { return fr_op_conv2d_ex(d, nullptr, stream); }
 
-// The tile ids fr_op_conv2d_ex hands to launch_conv (0 = the cost model's choice, an implicit-GEMM tile too)
-static bool op_tile_is_igemm(int tile) {
-    if (tile == 0) return true;
-    const int t = tile - 1;
-    return (t >= 0 && t < NUM_TILE_IDS && t != FR_TILE_BAND) || t == TILE_64x64_S3 || t == TILE_64x64 || t == TILE_32x64_S3;
-}
-
 int fr_op_conv2d_ex(const fr_conv_desc* d, const fr_conv_ext* e, void* stream) {
     if (!d || !d->x || !d->w || !d->y || d->B <= 0 || d->Cin <= 0 || d->Cin % 8 || d->Cx % 8 || d->x_off % 8 ||
         d->Cout <= 0 || d->Cout % 8 || d->Cy % 8 || d->y_off % 8 || d->Npad % 128 || d->Kpad % 64 ||
@@ -2839,16 +2350,14 @@ int fr_op_conv2d_ex(const fr_conv_desc* d, const fr_conv_ext* e, void* stream) {
             set_error(std::string("fr_op_conv2d_ex: ") + why);
             return FR_ERR_ARG;
         };
-        const int tile = d->tile;
-        const bool igemm = op_tile_is_igemm(tile);
-        const bool wring = tile == FR_TILE_WRING + 1, small = tile == FR_TILE_SMALL + 1, direct = tile == FR_TILE_DIRECT + 1;
+        const int tile = d->tile;  // its kernel takes a field or not: convs.cpp's table
+        const int takes = op_tile_takes(tile);
         if (e->amax_slots < 0) return refuse("amax_slots < 0");
         if (e->amax_slots > 0) a.amax_slots = e->amax_slots;
         if (e->x2) {
             if (d->dtype == FR_DTYPE_FP8) return refuse("the K-concatenated projection (x2) has no fp8 kernel");
-            if (!igemm && !wring && !small)
-                return refuse("the K-concatenated projection (x2) runs on the implicit-GEMM tiles, FR_TILE_WRING and "
-                              "FR_TILE_SMALL only (not band / rows / img / direct)");
+            if (!(takes & CONV_TAKES_X2))
+                return refuse(("the K-concatenated projection (x2) runs only on " + conv_takers(CONV_TAKES_X2)).c_str());
             if (e->st2 <= 0 || e->H2 <= 0 || e->W2 <= 0 || e->C2 <= 0 || e->x2_off < 0 || e->Cx2 % 8 || e->x2_off % 8 ||
                 d->Cin % 64 || e->C2 % 64 || a.K + e->C2 > d->Kpad || e->x2_off + e->C2 > e->Cx2 ||
                 (a.Ho - 1) * e->st2 >= e->H2 || (a.Wo - 1) * e->st2 >= e->W2)
@@ -2860,12 +2369,11 @@ int fr_op_conv2d_ex(const fr_conv_desc* d, const fr_conv_ext* e, void* stream) {
         }
         if (e->y_bf16) {
             if (d->dtype != FR_DTYPE_F16 || d->res || d->y2) return refuse("y_bf16 needs FR_DTYPE_F16 and neither res nor y2");
-            if (!igemm && !wring && !small && !direct)
-                return refuse("y_bf16 runs on the implicit-GEMM tiles, FR_TILE_WRING, FR_TILE_SMALL and FR_TILE_DIRECT only");
+            if (!(takes & CONV_TAKES_Y_BF16)) return refuse(("y_bf16 runs only on " + conv_takers(CONV_TAKES_Y_BF16)).c_str());
             a.y_bf16 = 1;
         }
         if (e->splitk_cnt) {
-            if (!igemm || d->dtype == FR_DTYPE_FP8) return refuse("splitk_cnt (in-launch split-K) is for the implicit-GEMM tiles only");
+            if (!(takes & CONV_TAKES_SPLITK_CNT) || d->dtype == FR_DTYPE_FP8) return refuse("splitk_cnt (in-launch split-K) is for the implicit-GEMM tiles only");
             // (the in-launch slabs are addressed by 32-bit buffer offsets)
             if (d->split_k > 1 && (size_t)d->split_k * a.M * a.Npad * sizeof(float) >= 0x7fffffffull)
                 return refuse("splitk_cnt: the partial workspace must stay below 2 GiB");
@@ -2883,108 +2391,10 @@ int fr_op_conv2d_ex(const fr_conv_desc* d, const fr_conv_ext* e, void* stream) {
         FR_HIP_CHECK(launch_conv_fp8(a, (hipStream_t)stream));
         return FR_OK;
     }
-    if (d->tile == FR_TILE_BAND + 1) {
-        int TH, variant;
-        if (!band_plan(a, &TH, &variant)) { set_error("fr_op_conv2d: band kernel not applicable"); return FR_ERR_ARG; }
-        FR_HIP_CHECK(launch_conv_band(a, TH, variant, (hipStream_t)stream));
-        return FR_OK;
-    }
-    if (d->tile == FR_TILE_WRING + 1) {
-        // the substep images, packed on the stream into stream-ordered scratch on every call (no cache
-        // keyed on the caller's weight pointer: new weights in the same buffer are always repacked)
-        a.wimg = (const bf16_t*)1;
-        if (!wring_supported(a)) { set_error("fr_op_conv2d: wring kernel not applicable"); return FR_ERR_ARG; }
-        hipStream_t st = (hipStream_t)stream;
-        void* tw = nullptr;
-        FR_HIP_CHECK(hipMallocAsync(&tw, wring_packed_elems(a.Kpad, a.Npad) * sizeof(bf16_t), st));
-        FR_HIP_CHECK(wring_pack_weights(a.w, a.Kpad, a.Npad, (bf16_t*)tw, st));
-        a.wimg = (const bf16_t*)tw;
-        FR_HIP_CHECK(launch_conv_wring(a, st));
-        FR_HIP_CHECK(hipFreeAsync(tw, st));
-        return FR_OK;
-    }
-    if (d->tile == FR_TILE_SMALL + 1) {
-        const int sp = d->split_k > 1 ? d->split_k : 1;  // KS | NF << 8 (conv_small.hip)
-        if (!small_split_ok(sp) || !small_supported(a, (sp >> 8) ? (sp >> 8) : 4)) {
-            set_error("fr_op_conv2d: small-M kernel not applicable");
-            return FR_ERR_ARG;
-        }
-        FR_HIP_CHECK(launch_conv_small(a, sp, (hipStream_t)stream));
-        return FR_OK;
-    }
-    if (d->tile == FR_TILE_DIRECT + 1) {
-        if (!direct_supported(a)) { set_error("fr_op_conv2d: direct kernel not applicable"); return FR_ERR_ARG; }
-        FR_HIP_CHECK(launch_conv_direct(a, 0, (hipStream_t)stream));
-        return FR_OK;
-    }
-    if (d->tile == FR_TILE_ROWS + 1) {
-        // the op API takes [Npad][Kpad] rows: pack the weight image, the class-bias and negf tables into
-        // stream-ordered scratch (the tables built on the host from the caller's device vectors)
-        a.wimg = (const bf16_t*)1;
-        a.ep = a.negf = (const float*)1;
-        if (!rows_supported(a)) { set_error("fr_op_conv2d: rows kernel not applicable"); return FR_ERR_ARG; }
-        hipStream_t st = (hipStream_t)stream;
-        FR_HIP_CHECK(hipStreamSynchronize(st));
-        std::vector<float> ep((size_t)9 * a.Npad, 0.f), nf(a.Npad, a.act == 1 ? 0.f : 1.f);
-        if (a.bias9) FR_HIP_CHECK(hipMemcpy(ep.data(), a.bias9, ep.size() * sizeof(float), hipMemcpyDeviceToHost));
-        else if (a.bias) {
-            FR_HIP_CHECK(hipMemcpy(ep.data(), a.bias, a.Cout * sizeof(float), hipMemcpyDeviceToHost));
-            for (int k = 1; k < 9; ++k) std::copy(ep.begin(), ep.begin() + a.Npad, ep.begin() + k * a.Npad);
-        }
-        if (a.act == 2) FR_HIP_CHECK(hipMemcpy(nf.data(), a.slope, a.Cout * sizeof(float), hipMemcpyDeviceToHost));
-        void *tw = nullptr, *te = nullptr, *tn = nullptr;
-        FR_HIP_CHECK(hipMalloc(&tw, rows_packed_elems(a.Cout) * sizeof(bf16_t)));
-        FR_HIP_CHECK(hipMalloc(&te, ep.size() * sizeof(float)));
-        FR_HIP_CHECK(hipMalloc(&tn, nf.size() * sizeof(float)));
-        FR_HIP_CHECK(hipMemcpy(te, ep.data(), ep.size() * sizeof(float), hipMemcpyHostToDevice));
-        FR_HIP_CHECK(hipMemcpy(tn, nf.data(), nf.size() * sizeof(float), hipMemcpyHostToDevice));
-        FR_HIP_CHECK(rows_pack_weights(a.w, a.Kpad, a.Cout, (bf16_t*)tw, st));
-        a.wimg = (const bf16_t*)tw;
-        a.ep = (const float*)te;
-        a.negf = (const float*)tn;
-        int dev = 0, ncu = 256;
-        hipDeviceProp_t prop;
-        if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess) ncu = prop.multiProcessorCount;
-        FR_HIP_CHECK(launch_conv_rows(a, ncu, st));
-        FR_HIP_CHECK(hipStreamSynchronize(st));
-        (void)hipFree(tw);
-        (void)hipFree(te);
-        (void)hipFree(tn);
-        return FR_OK;
-    }
-    if (d->tile == FR_TILE_IMG28 + 1 || d->tile == FR_TILE_IMG56 + 1) {
-        const bool w28 = d->tile == FR_TILE_IMG28 + 1;
-        int ic = 0;
-        if (!img_shape_ok(a, &ic) || ic != (w28 ? 128 : 64)) {
-            set_error(std::string("fr_op_conv2d: ") + (w28 ? "img28" : "img56") + " kernel not applicable");
-            return FR_ERR_ARG;
-        }
-        // the op API takes [Npad][Kpad] rows: pack the K-step slice images into stream-ordered scratch
-        hipStream_t st = (hipStream_t)stream;
-        void* tmp = nullptr;
-        FR_HIP_CHECK(hipMallocAsync(&tmp, img_packed_elems(ic) * sizeof(bf16_t), st));
-        FR_HIP_CHECK(img_pack_weights(a.w, a.Kpad, ic, (bf16_t*)tmp, st));
-        a.wimg = (const bf16_t*)tmp;
-        // activation negative-side factor: the PReLU slopes, 0 (ReLU) or 1 (none)
-        void* nf = nullptr;
-        FR_HIP_CHECK(hipMallocAsync(&nf, (size_t)a.Npad * sizeof(float), st));
-        if (a.act == 2) {
-            FR_HIP_CHECK(hipMemsetD32Async((hipDeviceptr_t)nf, 0, a.Npad, st));
-            FR_HIP_CHECK(hipMemcpyAsync(nf, a.slope, (size_t)a.Cout * sizeof(float), hipMemcpyDeviceToDevice, st));
-        } else {
-            const float one = a.act == 1 ? 0.f : 1.f;
-            uint32_t bits;
-            std::memcpy(&bits, &one, 4);
-            FR_HIP_CHECK(hipMemsetD32Async((hipDeviceptr_t)nf, (int)bits, a.Npad, st));
-        }
-        a.negf = (const float*)nf;
-        FR_HIP_CHECK(w28 ? launch_conv_img28(a, st) : launch_conv_img56(a, st));
-        FR_HIP_CHECK(hipFreeAsync(tmp, st));
-        FR_HIP_CHECK(hipFreeAsync(nf, st));
-        return FR_OK;
-    }
+    if (op_tile_forced_kind(d->tile))  // a specialised kernel (split_k: its own split, conv_small.hip's KS | NF << 8)
+        return run_forced_kind(d->tile, a, d->split_k > 1 ? d->split_k : 1, (hipStream_t)stream);
     if (d->tile > 0) {
-        if (d->tile > NUM_TILE_IDS && d->tile - 1 != TILE_64x64_S3 && d->tile - 1 != TILE_64x64 && d->tile - 1 != TILE_32x64_S3) {
+        if (!op_tile_is_igemm(d->tile)) {
             set_error("fr_op_conv2d: bad tile");
             return FR_ERR_ARG;
         }

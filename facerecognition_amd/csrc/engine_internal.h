@@ -1,5 +1,6 @@
-// What engine.cpp (blob loader, plan builders, conv selection, forward, C ABI) and stages.cpp (the fused-stage
-// kinds) share: the handle, the plan's records and a few helpers.  Nothing here is part of the library's ABI.
+// What engine.cpp (blob loader, plan builders, forward, C ABI), stages.cpp (the fused-stage kinds) and convs.cpp (the
+// conv kernel kinds: selection, tuning, launch) share: the handle, the plan's records and a few helpers.  Nothing
+// here is part of the library's ABI.
 #pragma once
 #include <mutex>
 #include <string>
@@ -224,6 +225,8 @@ struct fr_handle {
 
 namespace fr {
 
+constexpr int FR_SPLITK_TILES = 1 << 16;  // in-launch split-K tile counters per handle
+
 // ------------------------------------------------------------------ engine.cpp
 int dev_alloc(void** p, size_t bytes);
 
@@ -238,8 +241,6 @@ int upload(fr_handle* h, T** dst, const std::vector<T>& src) {
     return FR_OK;
 }
 
-// One conv op: its ConvArgs from the plan's tensors and weights, then the kernel choice.
-int run_conv_op(fr_handle* h, const Op& op, int B, int f16, hipStream_t s);
 int run_maxpool_op(fr_handle* h, const Op& op, int B, int f16, hipStream_t s);
 
 // Per-op skip rule: a stage op runs when its plan entry says so; its member ops run when it does not (Op::grp).
@@ -313,6 +314,25 @@ int run_stage(fr_handle* h, const Op& op, int B, int f16, const std::vector<char
 int measure_stage(fr_handle* h, const Op& op, int B, int f16, const std::vector<char>& stage_run, hipStream_t s);
 // fr_debug_plan's line of a stage op.
 std::string stage_plan_line(const fr_handle* h, const Op& op, int B);
+
+// ------------------------------------------------------------------ convs.cpp
+// Whether kernel choices are measured per shape and batch size (FR_AB autotune, default on).
+bool autotune_enabled();
+// Packs, at load time, the operands of every specialised kernel that applies to a conv of the plan.
+int pack_conv_weights(fr_handle* h);
+// One conv op: its ConvArgs from the plan's tensors and weights, then the kernel choice and the launch.
+int run_conv_op(fr_handle* h, const Op& op, int B, int f16, hipStream_t s);
+// fr_debug_plan's line of a conv or head op.
+std::string conv_plan_line(const fr_handle* h, const Op& op, int B);
+// The op API (fr_op_conv2d_ex), by descriptor tile id (0 = automatic, 1 + FR_TILE_*): whether the id names an
+// implicit-GEMM tile; the extension fields its kernel takes, and the kernels that take a field (for the refusal);
+// whether a specialised kernel claims it, and that kernel's checked launch on the caller's [Npad][Kpad] rows.
+enum { CONV_TAKES_X2 = 1, CONV_TAKES_Y_BF16 = 2, CONV_TAKES_SPLITK_CNT = 4 };
+bool op_tile_is_igemm(int tile);
+int op_tile_takes(int tile);
+std::string conv_takers(int field);
+bool op_tile_forced_kind(int tile);
+int run_forced_kind(int tile, ConvArgs& a, int split, hipStream_t s);
 
 }  // namespace fr
 

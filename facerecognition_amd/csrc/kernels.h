@@ -1,4 +1,4 @@
-// Internal launcher interface between the C-ABI/graph runner (engine.cpp) and the
+// Internal launcher interface between the C-ABI/graph runner (engine.cpp, stages.cpp, convs.cpp) and the
 // HIP kernels (conv_igemm.hip, misc.hip, match.hip).  Not part of the public ABI.
 #pragma once
 #include "common.h"
@@ -8,9 +8,7 @@ namespace fr {
 // Conv tile variants (BM pixels x BN channels, 4 waves each).
 enum { TILE_128x128 = 0, TILE_256x64 = 1, TILE_128x64 = 2, TILE_64x128 = 3,
        TILE_128x128_S3 = 4, TILE_256x128 = 5, TILE_128x256 = 6,  // *_S3 / 8-wave tiles: 3-stage DMA ring
-       TILE_128x64_S3 = 8, TILE_64x128_S3 = 9, NUM_TILE_IDS = 10,     // (7 = the band kernel's id in the ABI)
-       TILE_WRING = 13,    // conv_wring.hip (= FR_TILE_WRING), an autotuner candidate beside the igemm tiles
-       TILE_DIRECT = 14,   // conv_direct.hip (= FR_TILE_DIRECT), the same
+       TILE_128x64_S3 = 8, TILE_64x128_S3 = 9, NUM_TILE_IDS = 10,     // (7 and 10 .. 16: the specialised kernels' FR_TILE_* ids)
        TILE_64x64_S3 = 17, TILE_64x64 = 18, TILE_32x64_S3 = 19 };  // round 6: small-M GEMMs (IRV1 Block8: M = 2304) over more CUs
 
 // Implicit-GEMM convolution, NHWC bf16 in/out, f32 accumulate, fused epilogue.
@@ -91,7 +89,7 @@ void head_plan(int M, int Cout, int Kpad, int* tile, int* split);  // the embedd
 int conv_tile_bm(int tile);
 int conv_tile_bn(int tile);
 
-// Launches a.tile with a.split_k; returns hipError_t.
+// Launches implicit-GEMM tile a.tile with a.split_k; returns hipError_t.
 hipError_t launch_conv(const ConvArgs& a, hipStream_t s);
 // Row-band direct 3x3/s1/p1 conv (conv_band.hip): applicability/params, launch.
 bool band_plan(const ConvArgs& a, int* cfg, int* variant);
