@@ -40,6 +40,9 @@ FR_OPTIM_CHUNK = 65536
 FR_OPTIM_MAX_GROUPS = 32
 FR_ERR_ARG = -1
 FR_ERR_STAGE = -6
+FR_TILE_128x128 = 0
+FR_TILE_128x64 = 2
+FR_TILE_64x128 = 3
 FR_TILE_BAND = 7
 FR_TILE_IMG28 = 10
 FR_TILE_IMG56 = 11

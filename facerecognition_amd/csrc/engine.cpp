@@ -2387,7 +2387,13 @@ int fr_op_conv2d_ex(const fr_conv_desc* d, const fr_conv_ext* e, void* stream) {
         }
         a.w8 = (const uint8_t*)d->w; a.wscale = d->wscale; a.x_amax = d->x_amax;
         a.tile = conv_fp8_tile(a.M, a.Cout);
-        if (d->tile > 0) a.tile = d->tile - 1;
+        if (d->tile > 0) {  // conv_fp8.hip has three tiles; any other id would run the 128x128 one under a wrong name
+            a.tile = d->tile - 1;
+            if (a.tile != TILE_128x128 && a.tile != TILE_128x64 && a.tile != TILE_64x128) {
+                set_error("fr_op_conv2d: fp8 runs on FR_TILE_128x128, FR_TILE_128x64 and FR_TILE_64x128 only");
+                return FR_ERR_ARG;
+            }
+        }
         FR_HIP_CHECK(launch_conv_fp8(a, (hipStream_t)stream));
         return FR_OK;
     }

@@ -858,7 +858,8 @@ typedef struct fr_conv_desc {
     const float* bias9;
     /* dtype == FR_DTYPE_FP8: w is e4m3 bytes [Npad][Kpad] (Kpad % 128 == 0, Cin % 64 == 0), wscale [Npad]
      * per-output-channel f32 scales, x_amax -> the input's max |x| (device f32; the activation scale is
-     * the power of two 2^e with max|x| / 2^e <= 448); x, res, y, y2 are bf16.  y_amax (any dtype, may
+     * the power of two 2^e with max|x| / 2^e <= 448); x, res, y, y2 are bf16; a forced tile must be
+     * FR_TILE_128x128, FR_TILE_128x64 or FR_TILE_64x128 (any other id: FR_ERR_ARG).  y_amax (any dtype, may
      * be NULL): the epilogue atomically raises it to max |y| of what it stores (caller zeroes it). */
     const float* wscale;
     const float* x_amax;

@@ -228,7 +228,7 @@ def unit_bn(eps, n=1 << 17):
     return g[k], rv[k]
 
 
-def selection_state_dict(seed=0):
+def selection_state_dict(seed=0, magnitude=None):
     """synth_state_dict("iresnet100") with the convs of selection_convs replaced by selections:
       * every output channel n has one nonzero weight, at fused_ref.selected_position: 1 on conv1 and the downsample,
         2^-2 on conv2;
@@ -239,7 +239,10 @@ def selection_state_dict(seed=0):
         differs between border classes exactly where the selected tap leaves the image;
       * the PReLU slopes are 1/2, 1/4, 1/8, varying by channel.
     Every stored value of the four kernels is then (x + b9) or (x + b9) slope or (x + t / 4), correctly rounded: a
-    sum of at most two exactly representable terms times a power of two, which no summation order can change."""
+    sum of at most two exactly representable terms times a power of two, which no summation order can change.
+    `magnitude`: a function (block prefix, member) -> the nonzero weight of that conv, or None for the value above
+    (tests/fp8_ref.py: 0.875 and 0.21875 = 7/8 and 7/32, which weights.quantize_fp8 turns into the e4m3 value 448 with
+    the scales 2^-9 and 2^-11 exactly; the folded pre-conv shift then enters b9 as 0.875 t1, still a short dyadic)."""
     sd = dict(Wt.synth_state_dict(ARCH))
     g, rv = unit_bn(Wt.BN_EPS[ARCH])
 
@@ -255,7 +258,8 @@ def selection_state_dict(seed=0):
         cout, cin, kh, kw = shape
         tap, ci = selected_position(shape, blk)
         w = np.zeros((cout, cin, kh * kw), np.float32)
-        w[np.arange(cout), ci, tap] = 0.25 if member == "conv2" else 1.0
+        mag = None if magnitude is None else magnitude(pre, member)
+        w[np.arange(cout), ci, tap] = mag if mag is not None else (0.25 if member == "conv2" else 1.0)
         sd[key] = w.reshape(shape)
         if member == "conv2":
             unit(pre + ".bn3", cout, np.zeros(cout))

@@ -77,6 +77,17 @@ def test_projection_refused_with_fp8():
     assert "fr_op_conv2d_ex" in _refused(d, _ext(), "fp8")
 
 
+@pytest.mark.parametrize("tile", [1, 4, 5, 6, 8, 9, N.FR_TILE_BAND, N.FR_TILE_WRING, N.FR_TILE_SMALL, N.FR_TILE_64x64, 40])
+def test_fp8_refuses_tiles_it_does_not_have(tile):
+    """conv_fp8.hip has the 128x128, 128x64 and 64x128 tiles; any other id used to run the 128x128 kernel."""
+    d = _desc(dtype=N.FR_DTYPE_FP8, wscale=P, x_amax=P, Kpad=640, tile=tile + 1)
+    L = N.lib()
+    L.fr_op_avgpool(None, 1, 1, 1, 8, None, 0, None)
+    for rc in (L.fr_op_conv2d(ctypes.byref(d), None), L.fr_op_conv2d_ex(ctypes.byref(d), ctypes.byref(_ext(False)), None)):
+        msg = L.fr_last_error().decode()
+        assert rc == N.FR_ERR_ARG and "fr_op_conv2d" in msg and "fp8" in msg and "FR_TILE_64x128" in msg, (rc, msg)
+
+
 def test_projection_forced_kernels_keep_their_own_shape_checks():
     _refused(_desc(tile=N.FR_TILE_WRING + 1, Kpad=704), _ext(), "wring")  # K1 + C2 != Kpad
     d = _desc(tile=N.FR_TILE_SMALL + 1, Kh=7, Kw=7, pad_h=3, pad_w=3, Kpad=49 * 64 + 64)  # more than 32 taps

@@ -38,45 +38,27 @@ def _fp8(t):
 
 
 def _conv_fp8(x, w, *, stride, pad, bias=None, act=0, slope=None, res=None):
-    """Run fr_op_conv2d with dtype FP8. x: cuda bf16 NHWC; w: cpu f32 [Cout,Cin,kh,kw]."""
-    import ctypes
+    """Run fr_op_conv2d with dtype FP8 (tests/fp8_op.py builds the descriptor). x: cuda bf16 NHWC; w: cpu f32
+    [Cout,Cin,kh,kw]."""
+    from tests import fp8_op
     dev = x.device
     B, H, W, Cx = x.shape
     cout, cin, kh, kw = w.shape
     K = kh * kw * cin
-    npad, kpad = (cout + 127) // 128 * 128, (K + 127) // 128 * 128
-    wk = w.permute(0, 2, 3, 1).reshape(cout, K)
-    s = wk.abs().amax(dim=1) / 448.0
-    q = _fp8(wk / s[:, None])
-    w8 = torch.zeros((npad, kpad), dtype=torch.uint8)
-    w8[:cout, :K] = q.to(torch.float8_e4m3fn).view(torch.uint8)
-    sc = torch.zeros(npad)
-    sc[:cout] = s
+    w8, sc, codes = fp8_op.quantize_weights(w)
+    s, q = sc[:cout], codes.reshape(cout, K)
     Ho = (H + 2 * pad[0] - kh) // stride[0] + 1
     Wo = (W + 2 * pad[1] - kw) // stride[1] + 1
     y = torch.zeros((B, Ho, Wo, cout), dtype=torch.bfloat16, device=dev)
     xa = x.float().abs().max().reshape(1).to(dev)
     ya = torch.zeros(1, device=dev)
-    keep = [w8.to(dev), sc.to(dev)]
-    d = N.FrConvDesc()
-    d.x, d.B, d.H, d.W, d.Cx, d.x_off, d.Cin = x.data_ptr(), B, H, W, Cx, 0, cin
-    d.w, d.Cout, d.Kh, d.Kw = keep[0].data_ptr(), cout, kh, kw
-    d.stride_h, d.stride_w, d.pad_h, d.pad_w, d.Npad, d.Kpad = stride[0], stride[1], pad[0], pad[1], npad, kpad
 
-    def dptr(t):
-        if t is None:
-            return None
-        t = t.to(dev).float().contiguous()
-        keep.append(t)
-        return t.data_ptr()
+    def dev32(t):
+        return None if t is None else t.to(dev).float().contiguous()
 
-    d.bias, d.act, d.slope = dptr(bias), act, dptr(slope)
-    if res is not None:
-        d.res, d.Cres, d.res_off = res.data_ptr(), res.shape[-1], 0
-    d.y, d.Cy, d.y_off = y.data_ptr(), cout, 0
-    d.Ho, d.Wo, d.dtype, d.tile = Ho, Wo, N.FR_DTYPE_FP8, 0
-    d.wscale, d.x_amax, d.y_amax = keep[1].data_ptr(), xa.data_ptr(), ya.data_ptr()
-    N.check(N.lib().fr_op_conv2d(ctypes.byref(d), N.stream_ptr()), "fr_op_conv2d fp8")
+    rc = fp8_op.launch(x, w8.to(dev), sc.to(dev), xa, y, Cin=cin, Cout=cout, kh=kh, kw=kw, stride=stride, pad=pad,
+                       bias=dev32(bias), act=act, slope=dev32(slope), res=res, y_amax=ya)
+    N.check(rc, "fr_op_conv2d fp8")
     torch.cuda.synchronize()
     # fake-quant reference: activations / 2^e -> e4m3 -> * 2^e ; weights q * s
     e = math.ceil(math.log2(xa.item() / 448.0)) if xa.item() > 0 else 0

@@ -18,7 +18,8 @@ C  synthetic weights, the transition: slice_stats (worst element, pixel, channel
    by 16-bit roundings that another f32 summation order flips (test_stage_ref.py: no two of four orders more than 2x
    apart, the element statistic moving in steps of one storage ulp; a one-fragment or one-column fault 50x or more).
 
-Not covered: the e4m3 stage (conv_stage8.hip, tests/test_gpu_fp8.py), the layer3 variants 1-3 (bit-identical to the
+The e4m3 stage (conv_stage8.hip) and the e4m3 convs are held the same way by tests/test_gpu_fp8_exact.py (tests/fp8_ref.py).
+Not covered: the layer3 variants 1-3 (bit-identical to the
 default by test_gpu_stage.py::test_stage_variants_bit_identical), and batch sizes whose only difference is the grid.
 
 Measured on an MI355X.  A, B = 9, images 0, 4, 8: the largest |stored - float64| / bound per stage, kind of conv and
