@@ -210,11 +210,11 @@ static int prepare(const ConvKindDesc& d, ConvArgs& a, const ConvAlloc& alloc, h
     }
     if (d.negf && !a.negf) {
         if ((rc = alloc(&p, (size_t)a.Npad * sizeof(float)))) return rc;
-        const float fill = a.act == 1 ? 0.f : 1.f;
+        const float fill = a.act == ACT_RELU ? 0.f : 1.f;
         uint32_t bits;
         std::memcpy(&bits, &fill, 4);
         FR_HIP_CHECK(hipMemsetD32Async((hipDeviceptr_t)p, (int)bits, a.Npad, s));
-        if (a.act == 2 && a.slope) FR_HIP_CHECK(hipMemcpyAsync(p, a.slope, a.Cout * sizeof(float), hipMemcpyDeviceToDevice, s));
+        if (a.act == ACT_PRELU && a.slope) FR_HIP_CHECK(hipMemcpyAsync(p, a.slope, a.Cout * sizeof(float), hipMemcpyDeviceToDevice, s));
         a.negf = (const float*)p;
     }
     if (d.ep && !a.ep) {
@@ -255,10 +255,6 @@ static ConvArgs conv_args(const fr_handle* h, const Op& op, int B, int f16, bool
         a.C2 = cw.C2; a.st2 = op.st2; a.K1 = cw.K1;
     }
     a.y = act_ptr(op.out); a.Cy = to.C; a.y_off = op.out_off;
-    if (op.out2 >= 0) {
-        a.y2 = act_ptr(op.out2); a.Cy2 = h->tensors[op.out2].C; a.y2_off = 0;
-        a.aff_s = cw.aff_s; a.aff_b = cw.aff_b;
-    }
     if (h->amax && h->need_amax[op.out]) {
         a.y_amax = h->amax + (size_t)op.out * FR_AMAX_SLOTS;
         a.amax_slots = FR_AMAX_SLOTS;

@@ -1,14 +1,8 @@
-// frhip engine: C-ABI handle, weight-blob loader, static per-arch forward plans and the
-// gallery/match entry points.  See include/frhip.h for the boundary contract and
-// DESIGN.md for the data layout.  The fused stages of a plan (their kinds, packers, launches) are in stages.cpp,
-// how a conv gets its kernel (the conv kernel kinds, the tuner, the op API's forced kernels) in convs.cpp.
-//
-// The forward plans restate the reference backbones as a list of fused ops:
-//   FR_ARCH_RESNET50_ARCFACE  models/arcface/arcface_model.py:118-132 + head :192-196
-//   FR_ARCH_IRESNET100        insightface iresnet100 (IBasicBlock; README.md:72)
-//   FR_ARCH_IRV1_FACENET      facenet_pytorch InceptionResnetV1 (facenet_model.py:12-16)
-// BN is folded into the conv weights/bias by the Python importer
-// (facerecognition_amd/weights.py); this file only knows tensor names.
+// frhip engine: the C-ABI handle, its activation memory and the forward that runs a handle's plan.  See
+// include/frhip.h for the boundary contract and DESIGN.md for the data layout.  What the networks are (the weight-blob
+// parser and the per-arch plan builders) is in plan.cpp, the fused stages of a plan (their kinds, packers, launches) in
+// stages.cpp, how a conv gets its kernel (the conv kernel kinds, the tuner, the op API's forced kernels) in convs.cpp,
+// the gallery and matcher entry points in gallery_api.cpp, the stateless op entry points in ops_api.cpp.
 #include <algorithm>
 #include <cmath>
 #include <cstdio>
@@ -88,13 +82,6 @@ using namespace fr;
 
 namespace {
 
-struct HostT {
-    std::vector<int64_t> dims;
-    std::vector<float> v;
-};
-
-int round_up(int x, int m) { return (x + m - 1) / m * m; }
-
 constexpr size_t FR_MAX_SPLIT_STAGES = 6;  // stage ops per plan (at most one per residual layer + the transition)
 
 void drop_graphs(fr_handle* h) {
@@ -129,754 +116,6 @@ void free_weights(fr_handle* h) {
     h->stages.clear();
     h->proj_w = h->proj_b = nullptr;
     h->proj_d = 0;
-}
-
-// ------------------------------------------------------------------ weight blob
-// FRW1 := "FRW1" u32 count { u32 name_len, name, u32 ndim, i64 dims[ndim], f32 data[prod] }*
-int parse_blob(const void* blob, size_t n, std::unordered_map<std::string, HostT>& out) {
-    const uint8_t* p = (const uint8_t*)blob;
-    const uint8_t* end = p + n;
-    auto need = [&](size_t k) { return (size_t)(end - p) >= k; };
-    if (!need(8) || std::memcmp(p, "FRW1", 4) != 0) {
-        set_error("weight blob: bad magic (expected FRW1)");
-        return FR_ERR_WEIGHTS;
-    }
-    p += 4;
-    uint32_t count;
-    std::memcpy(&count, p, 4);
-    p += 4;
-    for (uint32_t i = 0; i < count; ++i) {
-        uint32_t nl, nd;
-        if (!need(4)) goto trunc;
-        std::memcpy(&nl, p, 4);
-        p += 4;
-        if (!need(nl + 4)) goto trunc;
-        {
-            std::string name((const char*)p, nl);
-            p += nl;
-            std::memcpy(&nd, p, 4);
-            p += 4;
-            if (nd > 8 || !need(8ull * nd)) goto trunc;
-            HostT t;
-            t.dims.resize(nd);
-            std::memcpy(t.dims.data(), p, 8ull * nd);
-            p += 8ull * nd;
-            size_t cnt = 1;
-            for (auto d : t.dims) cnt *= (size_t)d;
-            if (!need(4 * cnt)) goto trunc;
-            t.v.resize(cnt);
-            std::memcpy(t.v.data(), p, 4 * cnt);
-            p += 4 * cnt;
-            out[name] = std::move(t);
-        }
-    }
-    return FR_OK;
-trunc:
-    set_error("weight blob: truncated");
-    return FR_ERR_WEIGHTS;
-}
-
-// ------------------------------------------------------------------ plan builder
-struct Builder {
-    fr_handle* h;
-    std::unordered_map<std::string, HostT>& W;
-    int rc = FR_OK;
-
-    int tensor(int H, int Wd, int C, const std::string& name = "") {
-        h->tensors.push_back({H, Wd, C, nullptr, name});
-        return (int)h->tensors.size() - 1;
-    }
-
-    const HostT* find(const std::string& n) {
-        auto it = W.find(n);
-        return it == W.end() ? nullptr : &it->second;
-    }
-
-    bool stem = false;  // next conv is the network stem: fold 1/255 + hi/lo split (see launch_preprocess)
-
-    bool pack_f16 = false;  // the conv being built reads an f16 tensor: f16 weights (set by conv_ds)
-
-    float round16(float v) const {  // stem hi/lo split in the activation dtype (bf16 for FR_DTYPE_FP8)
-        return pack_f16 ? host_h2f(host_f2h(v)) : host_bf2f(host_f2bf(v));
-    }
-
-    // Build one (possibly N-concatenated) conv weight: names[i].w is [Cout_i, kh, kw, Cin_w] f32.
-    // kcat (single name only): a 1x1 conv [Cout, 1, 1, c2] whose weights are appended to every row
-    // (K = kh*kw*cin + c2) and whose bias is added: a residual block's downsample folded into its last conv.
-    int make_convw(const std::vector<std::string>& names, int kh, int kw, int cin, int act, const std::string& aff,
-                   const std::string& kcat = "", int c2 = 0) {
-        const bool stem_split = stem;
-        stem = false;
-        DevConvW cw;
-        cw.Kh = kh;
-        cw.Kw = kw;
-        cw.Cin = cin;
-        cw.K = kh * kw * cin;
-        std::vector<float> wrows, bias, slope;
-        int cout = 0;
-        for (const auto& nm : names) {
-            const HostT* w = find(nm + ".w");
-            if (!w || w->dims.size() != 4 || w->dims[1] != kh || w->dims[2] != kw || w->dims[3] > cin) {
-                set_error("weights: missing or mis-shaped tensor " + nm + ".w");
-                rc = FR_ERR_WEIGHTS;
-                return -1;
-            }
-            const int co = (int)w->dims[0], ci = (int)w->dims[3];
-            if (stem_split && (ci != 3 || cin != 8)) {
-                set_error("plan: stem conv " + nm + " must have 3 input channels");
-                rc = FR_ERR_WEIGHTS;
-                return -1;
-            }
-            for (int o = 0; o < co; ++o)
-                for (int r = 0; r < kh; ++r)
-                    for (int s = 0; s < kw; ++s)
-                        for (int c = 0; c < cin; ++c) {
-                            if (stem_split) {
-                                // input channels are [q, q, 0, 0], q = 255*x: weights [hi, lo, 0, 0] of w/255
-                                const float wv = w->v[(((size_t)o * kh + r) * kw + s) * ci + (c % 3)] / 255.0f;
-                                const float hi = round16(wv);
-                                wrows.push_back(c < 3 ? hi : (c < 6 ? wv - hi : 0.f));
-                            } else {
-                                wrows.push_back(c < ci ? w->v[(((size_t)o * kh + r) * kw + s) * ci + c] : 0.f);
-                            }
-                        }
-            const HostT* b = find(nm + ".b");
-            for (int o = 0; o < co; ++o) bias.push_back(b ? b->v[o] : 0.f);
-            if (act == 2) {
-                const HostT* sl = find(nm + ".slope");
-                if (!sl) {
-                    set_error("weights: missing " + nm + ".slope");
-                    rc = FR_ERR_WEIGHTS;
-                    return -1;
-                }
-                for (int o = 0; o < co; ++o) slope.push_back(sl->v[o]);
-            }
-            cout += co;
-        }
-        cw.Cout = cout;
-        cw.K1 = cw.K;
-        if (!kcat.empty()) {
-            const HostT* w2 = find(kcat + ".w");
-            if (names.size() != 1 || !w2 || w2->dims.size() != 4 || w2->dims[0] != cout || w2->dims[1] != 1 ||
-                w2->dims[2] != 1 || w2->dims[3] != c2) {
-                set_error("weights: missing or mis-shaped tensor " + kcat + ".w");
-                rc = FR_ERR_WEIGHTS;
-                return -1;
-            }
-            std::vector<float> cat((size_t)cout * (cw.K + c2));
-            for (int o = 0; o < cout; ++o) {
-                std::copy(wrows.begin() + (size_t)o * cw.K, wrows.begin() + (size_t)(o + 1) * cw.K,
-                          cat.begin() + (size_t)o * (cw.K + c2));
-                std::copy(w2->v.begin() + (size_t)o * c2, w2->v.begin() + (size_t)(o + 1) * c2,
-                          cat.begin() + (size_t)o * (cw.K + c2) + cw.K);
-            }
-            wrows.swap(cat);
-            const HostT* b2 = find(kcat + ".b");
-            if (b2)
-                for (int o = 0; o < cout; ++o) bias[o] += b2->v[o];
-            cw.C2 = c2;
-            cw.K += c2;
-        }
-        cw.Npad = round_up(cout, 128);
-        cw.Kpad = round_up(cw.K, 64);
-        std::vector<bf16_t> packed((size_t)cw.Npad * cw.Kpad, 0);
-        const bool f16 = pack_f16;
-        for (int o = 0; o < cout; ++o)
-            for (int k = 0; k < cw.K; ++k) {
-                const float v = wrows[(size_t)o * cw.K + k];
-                packed[(size_t)o * cw.Kpad + k] = f16 ? host_f2h(v) : host_f2bf(v);
-            }
-        bias.resize(cw.Npad, 0.f);
-        if ((rc = upload(h, &cw.w, packed))) return -1;
-        if (h->dtype == FR_DTYPE_FP8 && names.size() == 1 && !stem_split && cin % 64 == 0 && kcat.empty()) {
-            const HostT* ws = find(names[0] + ".wscale");
-            if (ws) {  // e4m3 weights: the blob carries e4m3-representable values w/s and the scales s
-                if ((int)ws->v.size() != cout) {
-                    set_error("weights: mis-sized " + names[0] + ".wscale");
-                    rc = FR_ERR_WEIGHTS;
-                    return -1;
-                }
-                cw.Kpad8 = round_up(cw.K, 128);
-                std::vector<uint8_t> q((size_t)cw.Npad * cw.Kpad8, 0);
-                for (int o = 0; o < cout; ++o)
-                    for (int k = 0; k < cw.K; ++k) q[(size_t)o * cw.Kpad8 + k] = host_f2e4m3(wrows[(size_t)o * cw.K + k]);
-                std::vector<float> sc(ws->v);
-                sc.resize(cw.Npad, 0.f);
-                if ((rc = upload(h, &cw.w8, q))) return -1;
-                if ((rc = upload(h, &cw.wscale, sc))) return -1;
-                // the bf16 copy (debug / op paths) holds the dequantized weights
-                for (int o = 0; o < cout; ++o)
-                    for (int k = 0; k < cw.K; ++k)
-                        packed[(size_t)o * cw.Kpad + k] = host_f2bf(wrows[(size_t)o * cw.K + k] * ws->v[o]);
-                if (hipMemcpy(cw.w, packed.data(), packed.size() * sizeof(bf16_t), hipMemcpyHostToDevice) != hipSuccess) {
-                    set_error("hipMemcpy of dequantized fp8 weights failed");
-                    rc = FR_ERR_HIP;
-                    return -1;
-                }
-            }
-        }
-        if ((rc = upload(h, &cw.bias, bias))) return -1;
-        if (names.size() == 1) {
-            const HostT* b9 = find(names[0] + ".b9");
-            if (b9 && !kcat.empty()) {  // bias9 replaces `bias`, which carries the folded downsample's bias
-                set_error("plan: conv " + names[0] + " has both a border-class bias (.b9) and a K-concatenated "
-                          "downsample; the downsample bias would be dropped");
-                rc = FR_ERR_WEIGHTS;
-                return -1;
-            }
-            if (b9) {
-                if (b9->dims.size() != 2 || b9->dims[0] != 9 || b9->dims[1] != cout || kh != 3 || kw != 3) {
-                    set_error("weights: mis-shaped " + names[0] + ".b9 (expects [9, Cout] on a 3x3 conv)");
-                    rc = FR_ERR_WEIGHTS;
-                    return -1;
-                }
-                std::vector<float> t9((size_t)9 * cw.Npad, 0.f);
-                for (int c = 0; c < 9; ++c)
-                    for (int o = 0; o < cout; ++o) t9[(size_t)c * cw.Npad + o] = b9->v[(size_t)c * cout + o];
-                if ((rc = upload(h, &cw.bias9, t9))) return -1;
-            }
-        }
-        if (act == 2) {
-            slope.resize(cw.Npad, 0.f);
-            if ((rc = upload(h, &cw.slope, slope))) return -1;
-        }
-        if (!aff.empty()) {
-            const HostT* s = find(aff + ".s");
-            const HostT* t = find(aff + ".t");
-            if (!s || !t || (int)s->v.size() != cout || (int)t->v.size() != cout) {
-                set_error("weights: missing or mis-sized affine " + aff + ".s/.t");
-                rc = FR_ERR_WEIGHTS;
-                return -1;
-            }
-            std::vector<float> sv = s->v, tv = t->v;
-            sv.resize(cw.Npad, 0.f);
-            tv.resize(cw.Npad, 0.f);
-            if ((rc = upload(h, &cw.aff_s, sv))) return -1;
-            if ((rc = upload(h, &cw.aff_b, tv))) return -1;
-        }
-        h->convw.push_back(cw);
-        return (int)h->convw.size() - 1;
-    }
-
-    // conv op; returns output spatial size through the out tensor (must already exist).
-    void conv(const std::vector<std::string>& names, int in, int in_off, int cin, int out, int out_off, int kh, int kw,
-              int sh, int sw, int ph, int pw, int act, int res = -1, int res_off = 0, int out2 = -1,
-              const std::string& aff = "") {
-        conv_ds(names, in, in_off, cin, out, out_off, kh, kw, sh, sw, ph, pw, act, res, res_off, out2, aff, "", -1, 0, 1);
-    }
-
-    // conv whose residual is a downsample (1x1 conv `ds` of tensor x2 at stride st2) folded into its K
-    // (ds empty: a plain conv)
-    void conv_ds(const std::vector<std::string>& names, int in, int in_off, int cin, int out, int out_off, int kh,
-                 int kw, int sh, int sw, int ph, int pw, int act, int res, int res_off, int out2, const std::string& aff,
-                 const std::string& ds, int x2, int c2, int st2) {
-        if (rc) return;
-        Op op;
-        op.kind = OP_CONV;
-        op.in = in; op.in_off = in_off; op.cin = cin;
-        op.out = out; op.out_off = out_off;
-        op.res = res; op.res_off = res_off; op.out2 = out2;
-        op.kh = kh; op.kw = kw; op.sh = sh; op.sw = sw; op.ph = ph; op.pw = pw; op.act = act;
-        op.x2 = ds.empty() ? -1 : x2;
-        op.st2 = st2;
-        pack_f16 = h->dtype == FR_DTYPE_F16 || h->tensors[in].f16;
-        // inside an f16 section of a bf16 plan a residual must be f16 too and the output stays f16 (the kernels' y_bf16
-        // boundary store takes no residual)
-        const bool res_ok = res < 0 || (h->tensors[res].f16 && h->tensors[out].f16);
-        if (h->tensors[in].f16 && (!res_ok || out2 >= 0 || !ds.empty() || h->dtype != FR_DTYPE_BF16)) {
-            set_error("plan: f16 section conv " + names[0] + " with a residual / second output / projection");
-            rc = FR_ERR_ARG;
-            return;
-        }
-        op.wi = make_convw(names, kh, kw, cin, act, aff, ds, c2);
-        if (op.wi < 0) return;
-        const auto& ti = h->tensors[in];
-        const auto& to = h->tensors[out];
-        const int Ho = (ti.H + 2 * ph - kh) / sh + 1, Wo = (ti.W + 2 * pw - kw) / sw + 1;
-        const int cout = h->convw[op.wi].Cout;
-        if (Ho != to.H || Wo != to.W || out_off + cout > to.C || in_off + cin > ti.C ||
-            (res >= 0 && (h->tensors[res].H != Ho || res_off + cout > h->tensors[res].C)) ||
-            (op.x2 >= 0 && (h->tensors[x2].C != c2 || (Ho - 1) * st2 >= h->tensors[x2].H ||
-                            (Wo - 1) * st2 >= h->tensors[x2].W || cin % 64 != 0 || c2 % 64 != 0))) {
-            set_error("plan: shape mismatch at conv " + names[0]);
-            rc = FR_ERR_ARG;
-            return;
-        }
-        h->ops.push_back(op);
-    }
-
-    // whether a residual block's downsample folds into its last conv (igemm K-concatenation): not for
-    // e4m3 convs (the fp8 kernel has no projection source) and only on the 64-channel fast-K path;
-    // FR_AB no_ds_fuse keeps the separate downsample conv (A/B)
-    // whether conv `name` runs in e4m3 (FR_DTYPE_FP8 and the blob's plan gave it a .wscale)
-    bool is_fp8(const std::string& name) { return h->dtype == FR_DTYPE_FP8 && find(name + ".wscale"); }
-    bool fuse_ds(int cin, int c2, const std::string& pre) {
-        static const bool off = [] { return ab_int("no_ds_fuse", 0) != 0; }();
-        return !off && !is_fp8(pre + ".conv2") && !is_fp8(pre + ".downsample") && cin % 64 == 0 && c2 % 64 == 0;
-    }
-    void maxpool(int in, int out, int out_off, int k, int s, int p) {
-        Op op;
-        op.kind = OP_MAXPOOL;
-        op.in = in; op.out = out; op.out_off = out_off; op.pk = k; op.ps = s; op.pp = p;
-        op.cin = h->tensors[in].C;
-        h->ops.push_back(op);
-    }
-    void avgpool(int in, int out) {
-        Op op;
-        op.kind = OP_AVGPOOL;
-        op.in = in; op.out = out;
-        h->ops.push_back(op);
-    }
-    void head(int in) {
-        if (rc) return;
-        const HostT* w = find("head.w");
-        const auto& t = h->tensors[in];
-        const int K = t.H * t.W * t.C;
-        if (!w || w->dims.size() != 2 || w->dims[1] != K) {
-            set_error("weights: missing or mis-shaped head.w (expected [N, " + std::to_string(K) + "])");
-            rc = FR_ERR_WEIGHTS;
-            return;
-        }
-        W["head.__as_conv.w"] = HostT{{w->dims[0], 1, 1, K}, w->v};
-        if (find("head.b")) W["head.__as_conv.b"] = *find("head.b");
-        Op op;
-        op.kind = OP_HEAD;
-        op.in = in;
-        op.wi = make_convw({"head.__as_conv"}, 1, 1, K, 0, "");
-        if (op.wi < 0) return;
-        h->embed_dim = h->convw[op.wi].Cout;
-        h->ops.push_back(op);
-    }
-    // optional FaceNet projection "proj.w" [d, 512] + "proj.b" [d] after the (L2-normalized) head
-    void projection() {
-        if (rc) return;
-        const HostT* w = find("proj.w");
-        if (!w) return;
-        const HostT* bb = find("proj.b");
-        if (w->dims.size() != 2 || w->dims[1] != h->embed_dim || w->dims[1] > 1024 || !bb ||
-            (int64_t)bb->v.size() != w->dims[0]) {
-            set_error("weights: mis-shaped proj.w / proj.b (expects [d, " + std::to_string(h->embed_dim) + "], [d])");
-            rc = FR_ERR_WEIGHTS;
-            return;
-        }
-        if ((rc = upload(h, &h->proj_w, w->v))) return;
-        if ((rc = upload(h, &h->proj_b, bb->v))) return;
-        h->proj_d = (int)w->dims[0];
-    }
-
-    // A fused stage beside its member ops (stages.cpp).  Opening pushes the OP_STAGE op, ahead of the members the
-    // caller emits next, and returns its index.
-    int open_stage() {
-        Op op;
-        op.kind = OP_STAGE;
-        op.stage = (int)h->stages.size();
-        h->ops.push_back(op);
-        return (int)h->ops.size() - 1;
-    }
-    // Closing takes the finished record (its members in conv_ops): the members point at the stage, the kind's
-    // weight packer runs, and the record joins the plan.  fits = false: the members do not have the fused kernel's
-    // shapes, so the plan keeps the member ops only.
-    void close_stage(int st_op, StageRec& r, bool fits = true) {
-        if (rc) return;
-        if (!fits) {
-            h->ops.erase(h->ops.begin() + st_op);
-            for (auto& op : h->ops)
-                if (op.kind == OP_STAGE && op.stage >= (int)h->stages.size()) --op.stage;
-            return;
-        }
-        for (int oi : r.conv_ops) h->ops[oi].stage = h->ops[st_op].stage;
-        rc = pack_stage(h, r);
-        h->stages.push_back(r);
-    }
-};
-
-std::string L(int l, int i) { return "layer" + std::to_string(l) + "." + std::to_string(i); }
-
-void build_iresnet100(Builder& b) {
-    fr_handle* h = b.h;
-    h->in_size = 112;
-    const int in = b.tensor(112, 112, 8);
-    h->ops.push_back(Op{OP_PRE, -1, 0, 0, in});
-    // Each block's pre-conv bn1 is folded into its conv1 (weights scaled per input channel, the shift in
-    // a border-class bias table .b9: weights.fold_state_dict), so conv1 reads the previous block's output
-    // directly and no producer writes a second (bn1) output.
-    int x = b.tensor(112, 112, 64, "prelu");
-    b.stem = true;
-    b.conv({"conv1"}, in, 0, 8, x, 0, 3, 3, 1, 1, 1, 1, 2);
-    h->ops[h->ops.size() - 2].fuse_stem = true;  // conv_stem.hip (u8 input)
-    const int planes[4] = {64, 128, 256, 512}, nblk[4] = {3, 13, 30, 3};
-    int H = 112, C = 64;
-    // the bf16 layer3 stage stays open until layer4.0.conv1 is emitted: that conv becomes its tail
-    StageRec tail_rec;
-    int tail_st_op = -1;
-    for (int l = 0; l < 4; ++l) {
-        const int P = planes[l], Ho = H / 2;
-        // layer3 blocks 1.. (stride 1, 14x14x256) and layer2 / layer1 blocks 1..: also emitted as
-        // LDS-resident stage ops.  Under FR_DTYPE_FP8 the blocks whose convs carry .wscale (the mixed
-        // plan, weights.FP8_PLAN) form an e4m3 stage of their own (14x14x256 only), the rest bf16 stages.
-        int st_op = -1;
-        StageRec rec;
-        auto close_stage = [&](bool layer_end) {
-            // tail candidates: the bf16 layer3 stage (-> layer4.0.conv1) and the layer2 split stage (-> layer3.0.conv1)
-            if (st_op >= 0 && !b.rc && layer_end && !rec.fp8 &&
-                ((l == 2 && rec.parts == 1 && rec.C == 256) || (l == 1 && rec.parts == 2 && rec.C == 128 && rec.H == 28))) {
-                rec.out = x;
-                rec.nblk = (int)rec.t_tensors.size();
-                tail_rec = rec;
-                tail_st_op = st_op;
-            } else if (st_op >= 0) {
-                rec.out = x;
-                rec.nblk = (int)rec.t_tensors.size();
-                b.close_stage(st_op, rec);
-            }
-            st_op = -1;
-        };
-        for (int i = 0; i < nblk[l]; ++i) {
-            const bool s14 = stage_supported(1, Ho, Ho, P);
-            const int parts = split_stage_parts(Ho, Ho, P);
-            const std::string pre = L(l + 1, i);
-            const bool f8 = b.is_fp8(pre + ".conv1") && b.is_fp8(pre + ".conv2");
-            const bool mixed = b.is_fp8(pre + ".conv1") != b.is_fp8(pre + ".conv2");
-            const bool can = i >= 1 && P == C && !mixed && (f8 ? s14 : (s14 || parts > 0));
-            if (st_op >= 0 && (!can || f8 != rec.fp8)) close_stage(false);
-            if (can && st_op < 0) {
-                st_op = b.open_stage();
-                rec = StageRec{};
-                rec.kind = STAGE_LDS;
-                rec.in = x;
-                rec.parts = s14 ? 1 : parts;
-                rec.H = Ho;
-                rec.C = P;
-                rec.fp8 = f8;
-            }
-            const int Hin = i == 0 ? H : Ho, st = i == 0 ? 2 : 1;
-            const bool fuse = i == 0 && b.fuse_ds(P, C, pre);
-            // layer1.0 as one fused launch (conv_trans.hip) beside its member convs (measured per batch size)
-            const bool tr = i == 0 && fuse && !b.is_fp8(pre + ".conv1") && !b.is_fp8(pre + ".conv2") &&
-                            trans_supported(1, H, H, C, P, P, 9 * C, 9 * P + C);
-            const int tr_op = tr ? b.open_stage() : -1;
-            const int hmid = b.tensor(Hin, Hin, P, pre + ".prelu");
-            b.conv({pre + ".conv1"}, x, 0, C, hmid, 0, 3, 3, 1, 1, 1, 1, 2);
-            if (tail_st_op >= 0 && !b.rc) {  // layer4.0.conv1: the layer3 stage's tail when it fits, then close it
-                const int oi = (int)h->ops.size() - 1;
-                const Op& op = h->ops[oi];
-                const DevConvW& cw = h->convw[op.wi];
-                static const bool no_tail = ab_int("no_stage_tail", 0) != 0;  // FR_AB no_stage_tail: A/B timing
-                const int TC = tail_rec.C;
-                if (!no_tail && h->dtype != FR_DTYPE_FP8 && !cw.w8 && op.act == 2 && cw.slope && cw.Cout == 2 * TC &&
-                    cw.Npad >= 2 * TC && cw.Cin == TC && cw.Kh == 3 && cw.Kw == 3 && op.sh == 1 && op.sw == 1 && op.ph == 1 &&
-                    op.pw == 1 && op.in == tail_rec.out && op.in_off == 0 && op.out_off == 0 && op.res < 0 && op.x2 < 0 &&
-                    op.out2 < 0 && h->tensors[hmid].C == 2 * TC && !h->tensors[hmid].f16)
-                    tail_rec.tail_op = oi;
-                if (tail_rec.tail_op >= 0) tail_rec.conv_ops.push_back(oi);  // (the packer reads the blocks' 2 * nblk first)
-                b.close_stage(tail_st_op, tail_rec);
-                tail_st_op = -1;
-            }
-            int res = x;
-            if (i == 0 && !fuse) {
-                res = b.tensor(Ho, Ho, P, pre + ".downsample");
-                b.conv({pre + ".downsample"}, x, 0, C, res, 0, 1, 1, 2, 2, 0, 0, 0);
-            }
-            const int y = b.tensor(Ho, Ho, P, pre);
-            if (fuse)  // y = conv2(t) + downsample(x) in one K loop (no downsample tensor)
-                b.conv_ds({pre + ".conv2"}, hmid, 0, P, y, 0, 3, 3, st, st, 1, 1, 0, -1, 0, -1, "", pre + ".downsample",
-                          x, C, 2);
-            else
-                b.conv({pre + ".conv2"}, hmid, 0, P, y, 0, 3, 3, st, st, 1, 1, 0, res, 0);
-            if (tr && !b.rc) {
-                StageRec t;
-                t.kind = STAGE_TRANS;
-                t.in = x; t.out = y; t.nblk = 1; t.H = H; t.C = P;
-                t.conv_ops = {(int)h->ops.size() - 2, (int)h->ops.size() - 1};
-                t.t_tensors = {hmid};
-                t.x_tensors = {y};
-                b.close_stage(tr_op, t);
-            }
-            if (st_op >= 0 && !b.rc) {
-                rec.conv_ops.push_back((int)h->ops.size() - 2);
-                rec.conv_ops.push_back((int)h->ops.size() - 1);
-                rec.t_tensors.push_back(hmid);
-                rec.x_tensors.push_back(y);
-            }
-            x = y;
-            C = P;
-        }
-        close_stage(true);
-        H = Ho;
-    }
-    h->ex_tensor = x;  // fr_explain: Grad-CAM on layer4.2, which the head reads flattened (NHWC order)
-    h->ex_layout = 1;
-    b.head(x);
-}
-
-void build_resnet50(Builder& b) {
-    fr_handle* h = b.h;
-    h->in_size = 112;
-    const int in = b.tensor(112, 112, 8);
-    h->ops.push_back(Op{OP_PRE, -1, 0, 0, in});
-    const int c1 = b.tensor(56, 56, 64, "backbone.relu");
-    // conv1 + maxpool are also emitted as one launch (conv_stem_r50.hip) beside the member ops
-    const bool st = h->dtype != FR_DTYPE_FP8;
-    const int st_op = st ? b.open_stage() : -1;
-    b.stem = true;
-    b.conv({"backbone.conv1"}, in, 0, 8, c1, 0, 7, 7, 2, 2, 3, 3, 1);
-    int x = b.tensor(28, 28, 64, "backbone.maxpool");
-    b.maxpool(c1, x, 0, 3, 2, 1);
-    if (st && !b.rc) {
-        StageRec sr;
-        sr.kind = STAGE_STEM_R50;
-        sr.in = in; sr.out = x; sr.H = 112; sr.C = 8; sr.nblk = 1;
-        sr.conv_ops = {st_op + 1, st_op + 2};
-        const Op& cv = h->ops[st_op + 1];
-        const DevConvW& cw = h->convw[cv.wi];
-        if (!stem_r50_supported(112, 112, cv.cin, cw.K, cw.Kpad, cw.Cout) || cw.w8 || !cw.bias || cv.act != 1 ||
-            cv.sh != 2 || cv.ph != 3 || cv.res >= 0 || h->ops[st_op + 2].kind != OP_MAXPOOL) {
-            set_error("plan: ResNet-50 stem does not have the fused kernel's shape");
-            b.rc = FR_ERR_ARG;
-        }
-        b.close_stage(st_op, sr);
-    }
-    const int planes[4] = {64, 128, 256, 512}, nblk[4] = {3, 4, 6, 3}, strd[4] = {1, 2, 2, 2};
-    int H = 28, C = 64;
-    // layer3.1 .. layer3.5 (7x7x1024) are also emitted as one chain launch (conv_chain_r50.hip) beside their member
-    // convs; the faster is measured per batch size
-    int ch_op = -1, bn_op = -1;
-    StageRec ch, bn;
-    for (int l = 0; l < 4; ++l) {
-        const int P = planes[l];
-        for (int i = 0; i < nblk[l]; ++i) {
-            const std::string pre = "backbone." + L(l + 1, i);
-            // layer1 (28x28) likewise, one launch per block (conv_bneck28.hip): from layer1.0 when its downsample folds
-            // into conv3 (fuse_ds), else from layer1.1
-            const bool bn_ds = i == 0 && C == P && b.fuse_ds(P, C, pre);
-            if (l == 0 && bn_op < 0 && (bn_ds || i == 1) && h->dtype != FR_DTYPE_FP8 && bneck28_supported(H, H, 4 * P, P)) {
-                bn_op = b.open_stage();
-                bn.kind = STAGE_BNECK28;
-                bn.bn_ds = bn_ds;
-                bn.in = x; bn.H = H; bn.C = C; bn.nblk = nblk[l] - i;
-            }
-            if (l == 2 && i == 1 && h->dtype != FR_DTYPE_FP8 && H == 7 && chain_r50_supported(H, H, C, nblk[l] - 1)) {
-                ch_op = b.open_stage();
-                ch.kind = STAGE_CHAIN_R50;
-                ch.in = x; ch.H = H; ch.C = C; ch.nblk = nblk[l] - 1;
-            }
-            const size_t op0 = h->ops.size();
-            const int s = i == 0 ? strd[l] : 1;
-            const int Ho = (H + 2 - 3) / s + 1;
-            const int h1 = b.tensor(H, H, P);
-            b.conv({pre + ".conv1"}, x, 0, C, h1, 0, 1, 1, 1, 1, 0, 0, 1);
-            const int h2 = b.tensor(Ho, Ho, P);
-            b.conv({pre + ".conv2"}, h1, 0, P, h2, 0, 3, 3, s, s, 1, 1, 1);
-            int id = x;
-            const bool fuse = i == 0 && b.fuse_ds(P, C, pre);
-            if (i == 0 && !fuse) {
-                id = b.tensor(Ho, Ho, 4 * P, pre + ".downsample");
-                b.conv({pre + ".downsample"}, x, 0, C, id, 0, 1, 1, s, s, 0, 0, 0);
-            }
-            const int y = b.tensor(Ho, Ho, 4 * P, pre);
-            if (fuse)  // y = relu(conv3(h2) + downsample(x)) in one K loop
-                b.conv_ds({pre + ".conv3"}, h2, 0, P, y, 0, 1, 1, 1, 1, 0, 0, 1, -1, 0, -1, "", pre + ".downsample", x, C, s);
-            else
-                b.conv({pre + ".conv3"}, h2, 0, P, y, 0, 1, 1, 1, 1, 0, 0, 1, id, 0);
-            if (ch_op >= 0 && l == 2 && i >= 1)
-                for (size_t k = op0; k < h->ops.size(); ++k) ch.conv_ops.push_back((int)k);
-            if (bn_op >= 0 && l == 0) {
-                for (size_t k = op0; k < h->ops.size(); ++k) bn.conv_ops.push_back((int)k);
-                bn.x_tensors.push_back(y);
-            }
-            x = y;
-            C = 4 * P;
-            H = Ho;
-        }
-        if (bn_op >= 0 && l == 0) {
-            bn.out = x;
-            b.close_stage(bn_op, bn);
-        }
-        if (ch_op >= 0 && l == 2) {
-            ch.out = x;
-            b.close_stage(ch_op, ch);
-        }
-        if (l == 2) h->cut_l4in = x;  // fr_features_at: what layer4.0.conv1 and layer4.0.downsample read
-    }
-    h->ex_tensor = x;  // fr_explain: Grad-CAM on backbone.layer4 (the avg-pool's input)
-    h->ex_layout = 0;
-    const int pool = b.tensor(1, 1, C, "backbone.avgpool");
-    b.avgpool(x, pool);
-    b.head(pool);
-}
-
-void build_irv1(Builder& b) {
-    fr_handle* h = b.h;
-    h->in_size = 160;
-    const std::string m = "model.";
-    const int in = b.tensor(160, 160, 8);
-    h->ops.push_back(Op{OP_PRE, -1, 0, 0, in});
-    const int a = b.tensor(79, 79, 32, m + "conv2d_1a");
-    const int bb = b.tensor(77, 77, 32, m + "conv2d_2a");
-    const int c = b.tensor(77, 77, 64, m + "conv2d_2b");
-    const int d = b.tensor(38, 38, 64, m + "maxpool_3a");
-    const int e = b.tensor(38, 38, 80, m + "conv2d_3b");
-    const int f = b.tensor(36, 36, 192, m + "conv2d_4a");
-    int x = b.tensor(17, 17, 256, m + "conv2d_4b");
-    // bf16 plan: the high-resolution stem (input .. conv2d_4a) is stored and multiplied in f16.  Its
-    // activations are ~90 % of the forward's bf16 rounding drift (profiles/r02_irv1_drift_bf16_vs_f16.txt:
-    // 1.28e-2 of 1.61e-2 relative error is in place at conv2d_4b); f16 MFMAs run at the bf16 rate, and
-    // conv2d_4b writes bf16 for the rest of the network.  FR_IRV1_BF16_STEM=1 keeps it bf16 (A/B).
-    static const bool bf16_stem = [] {
-        const char* e = getenv("FR_IRV1_BF16_STEM");
-        return e && e[0] == '1';
-    }();
-    if (h->dtype == FR_DTYPE_BF16 && !bf16_stem)
-        for (int t : {in, a, bb, c, d, e, f}) h->tensors[t].f16 = true;
-    // Round 6: the f16 section also covers conv2d_4b's output, repeat_1 (Block35 x5) and mixed_6a's inner branch
-    // tensors; mixed_6a's convs and max-pool write the bf16 concat (the section boundary).  With the stem alone in f16
-    // the bf16 body still moved bs = 256 embeddings up to 8.9e-4 (1 - cos) from the fp32 oracle and flipped 7 % of
-    // the non-planted top-1 matches; f16 MFMAs run at the bf16 rate.  FR_AB irv1_f16_mid=0: the
-    // round-5 boundary at conv2d_4b (A/B).
-    // FR_AB irv1_f16_mid=2 (default): through repeat_2 (Block17 x10) too, the boundary at mixed_7a's outputs
-    static const int f16_mid = ab_int("irv1_f16_mid", 2);
-    const bool mid16 = h->dtype == FR_DTYPE_BF16 && !bf16_stem && f16_mid >= 1;
-    const bool mid16b = mid16 && f16_mid >= 2;
-    if (mid16) h->tensors[x].f16 = true;
-    b.stem = true;
-    // conv2d_1a .. conv2d_3b also as one launch (conv_stem160.hip) beside the member ops, measured per batch size
-    const int st_op = h->dtype != FR_DTYPE_FP8 ? b.open_stage() : -1;
-    b.conv({m + "conv2d_1a"}, in, 0, 8, a, 0, 3, 3, 2, 2, 0, 0, 1);
-    b.conv({m + "conv2d_2a"}, a, 0, 32, bb, 0, 3, 3, 1, 1, 0, 0, 1);
-    b.conv({m + "conv2d_2b"}, bb, 0, 32, c, 0, 3, 3, 1, 1, 1, 1, 1);
-    b.maxpool(c, d, 0, 3, 2, 0);
-    b.conv({m + "conv2d_3b"}, d, 0, 64, e, 0, 1, 1, 1, 1, 0, 0, 1);
-    if (st_op >= 0 && !b.rc) {
-        StageRec sr;
-        sr.kind = STAGE_STEM160;
-        sr.in = in; sr.out = e; sr.H = 160; sr.C = 80; sr.nblk = 1;
-        const int n = (int)h->ops.size();
-        sr.conv_ops = {n - 5, n - 4, n - 3, n - 2, n - 1};
-        const Op& o1 = h->ops[n - 5];
-        const Op& o2 = h->ops[n - 4];
-        const Op& o3 = h->ops[n - 3];
-        const Op& o4 = h->ops[n - 1];
-        const DevConvW& c1 = h->convw[o1.wi];
-        const DevConvW& c2 = h->convw[o2.wi];
-        const DevConvW& c3 = h->convw[o3.wi];
-        const DevConvW& c4 = h->convw[o4.wi];
-        bool ok = stem160_supported(160, 160, 8, c1.K, c2.K, c3.K, c4.K, c1.Cout, c2.Cout, c3.Cout, c4.Cout) &&
-                  h->tensors[in].f16 == h->tensors[e].f16 && o1.act == 1 && o2.act == 1 && o3.act == 1 && o4.act == 1;
-        for (const DevConvW* cw : {&c1, &c2, &c3, &c4}) ok = ok && cw->bias && !cw->bias9 && !cw->w8;
-        b.close_stage(st_op, sr, ok);  // not ok: no fused stem for these weights, the member ops only
-    }
-    b.conv({m + "conv2d_4a"}, e, 0, 80, f, 0, 3, 3, 1, 1, 0, 0, 1);
-    b.conv({m + "conv2d_4b"}, f, 0, 192, x, 0, 3, 3, 2, 2, 0, 0, 1);
-    // repeat_1: Block35 x5 @17x17. cat layout [t1 | t2 | b0 | b1 | b2]; conv2d reads [64:160].  Also emitted as one
-    // chain launch (conv_chain35.hip) beside its member convs; the faster is measured per batch size.
-    int c35_op = -1;
-    StageRec c35;
-    if (h->dtype != FR_DTYPE_FP8 && chain35_supported(17, 17, 256, 5)) {
-        c35_op = b.open_stage();
-        c35.kind = STAGE_CHAIN35;
-        c35.in = x; c35.H = 17; c35.C = 256; c35.nblk = 5;
-    }
-    for (int i = 0; i < 5; ++i) {
-        const std::string p = m + "repeat_1." + std::to_string(i) + ".";
-        const int cat = b.tensor(17, 17, 160);
-        if (mid16) h->tensors[cat].f16 = true;
-        b.conv({p + "branch1.0", p + "branch2.0", p + "branch0"}, x, 0, 256, cat, 0, 1, 1, 1, 1, 0, 0, 1);
-        b.conv({p + "branch1.1"}, cat, 0, 32, cat, 96, 3, 3, 1, 1, 1, 1, 1);
-        const int t = b.tensor(17, 17, 32);
-        if (mid16) h->tensors[t].f16 = true;
-        b.conv({p + "branch2.1"}, cat, 32, 32, t, 0, 3, 3, 1, 1, 1, 1, 1);
-        b.conv({p + "branch2.2"}, t, 0, 32, cat, 128, 3, 3, 1, 1, 1, 1, 1);
-        const int y = b.tensor(17, 17, 256, m + "repeat_1." + std::to_string(i));
-        if (mid16) h->tensors[y].f16 = true;
-        b.conv({p + "conv2d"}, cat, 64, 96, y, 0, 1, 1, 1, 1, 0, 0, 1, x, 0);
-        if (c35_op >= 0) {
-            for (int k = 5; k >= 1; --k) c35.conv_ops.push_back((int)h->ops.size() - k);
-            c35.x_tensors.push_back(y);
-        }
-        x = y;
-    }
-    if (c35_op >= 0) {
-        c35.out = x;
-        b.close_stage(c35_op, c35);
-    }
-    {  // mixed_6a
-        const std::string p = m + "mixed_6a.";
-        const int cat = b.tensor(8, 8, 896, m + "mixed_6a");
-        if (mid16b) h->tensors[cat].f16 = true;
-        b.conv({p + "branch0"}, x, 0, 256, cat, 0, 3, 3, 2, 2, 0, 0, 1);
-        const int u = b.tensor(17, 17, 192), v = b.tensor(17, 17, 192);
-        if (mid16) h->tensors[u].f16 = h->tensors[v].f16 = true;
-        b.conv({p + "branch1.0"}, x, 0, 256, u, 0, 1, 1, 1, 1, 0, 0, 1);
-        b.conv({p + "branch1.1"}, u, 0, 192, v, 0, 3, 3, 1, 1, 1, 1, 1);
-        b.conv({p + "branch1.2"}, v, 0, 192, cat, 384, 3, 3, 2, 2, 0, 0, 1);
-        b.maxpool(x, cat, 640, 3, 2, 0);
-        x = cat;
-    }
-    // repeat_2: Block17 x10 @8x8. cat layout [t1 | b0 | b1]; conv2d reads [128:384].  Also emitted as one
-    // chain launch (conv_chain.hip) beside its member convs; the faster is measured per batch size.
-    int ch_op = -1;
-    StageRec ch;
-    if (h->dtype != FR_DTYPE_FP8 && chain17_supported(8, 8, 896, 10)) {
-        ch_op = b.open_stage();
-        ch.kind = STAGE_CHAIN17;
-        ch.in = x; ch.H = 8; ch.C = 896; ch.nblk = 10;
-    }
-    for (int i = 0; i < 10; ++i) {
-        const std::string p = m + "repeat_2." + std::to_string(i) + ".";
-        const int cat = b.tensor(8, 8, 384);
-        const int t = b.tensor(8, 8, 128);
-        const int y = b.tensor(8, 8, 896, m + "repeat_2." + std::to_string(i));
-        if (mid16b) h->tensors[cat].f16 = h->tensors[t].f16 = h->tensors[y].f16 = true;
-        b.conv({p + "branch1.0", p + "branch0"}, x, 0, 896, cat, 0, 1, 1, 1, 1, 0, 0, 1);
-        b.conv({p + "branch1.1"}, cat, 0, 128, t, 0, 1, 7, 1, 1, 0, 3, 1);
-        b.conv({p + "branch1.2"}, t, 0, 128, cat, 256, 7, 1, 1, 1, 3, 0, 1);
-        b.conv({p + "conv2d"}, cat, 128, 256, y, 0, 1, 1, 1, 1, 0, 0, 1, x, 0);
-        if (ch_op >= 0)
-            for (int k = 4; k >= 1; --k) ch.conv_ops.push_back((int)h->ops.size() - k);
-        x = y;
-    }
-    if (ch_op >= 0) {
-        ch.out = x;
-        b.close_stage(ch_op, ch);
-    }
-    {  // mixed_7a
-        const std::string p = m + "mixed_7a.";
-        const int cat = b.tensor(3, 3, 1792, m + "mixed_7a");
-        const int u = b.tensor(8, 8, 768);
-        if (mid16b) h->tensors[u].f16 = true;
-        b.conv({p + "branch0.0", p + "branch1.0", p + "branch2.0"}, x, 0, 896, u, 0, 1, 1, 1, 1, 0, 0, 1);
-        b.conv({p + "branch0.1"}, u, 0, 256, cat, 0, 3, 3, 2, 2, 0, 0, 1);
-        b.conv({p + "branch1.1"}, u, 256, 256, cat, 384, 3, 3, 2, 2, 0, 0, 1);
-        const int v = b.tensor(8, 8, 256);
-        if (mid16b) h->tensors[v].f16 = true;
-        b.conv({p + "branch2.1"}, u, 512, 256, v, 0, 3, 3, 1, 1, 1, 1, 1);
-        b.conv({p + "branch2.2"}, v, 0, 256, cat, 640, 3, 3, 2, 2, 0, 0, 1);
-        b.maxpool(x, cat, 896, 3, 2, 0);
-        x = cat;
-    }
-    // repeat_3: Block8 x5 + final block8 (noReLU) @3x3. cat layout [t1 | b0 | b1]; conv2d reads [192:576].
-    for (int i = 0; i < 6; ++i) {
-        const std::string p = i < 5 ? m + "repeat_3." + std::to_string(i) + "." : m + "block8.";
-        const int cat = b.tensor(3, 3, 576);
-        b.conv({p + "branch1.0", p + "branch0"}, x, 0, 1792, cat, 0, 1, 1, 1, 1, 0, 0, 1);
-        const int t = b.tensor(3, 3, 192);
-        b.conv({p + "branch1.1"}, cat, 0, 192, t, 0, 1, 3, 1, 1, 0, 1, 1);
-        b.conv({p + "branch1.2"}, t, 0, 192, cat, 384, 3, 1, 1, 1, 1, 0, 1);
-        const int y = b.tensor(3, 3, 1792, i < 5 ? m + "repeat_3." + std::to_string(i) : m + "block8");
-        b.conv({p + "conv2d"}, cat, 192, 384, y, 0, 1, 1, 1, 1, 0, 0, i < 5 ? 1 : 0, x, 0);
-        x = y;
-    }
-    // fr_explain: the activation map of block8.conv2d's own output.  That conv writes conv + x, so fr_explain runs
-    // it once more without the residual into this scratch tensor (never the difference of two bf16 tensors)
-    if (!b.rc) {
-        h->ex_conv = (int)h->ops.size() - 1;
-        h->ex_tensor = b.tensor(3, 3, 1792);
-        h->ex_layout = 2;
-    }
-    const int pool = b.tensor(1, 1, 1792, m + "avgpool_1a");
-    b.avgpool(x, pool);
-    b.head(pool);
-    b.projection();
 }
 
 // ------------------------------------------------------------------ execution
@@ -1127,7 +366,6 @@ int forward(fr_handle* h, const void* in, int in_fmt, int B, float* out, int fla
                 if (op.res >= 0) rd[oi].push_back({op.res, op.res_off, op.res_off + cw.Cout});
                 if (op.x2 >= 0) rd[oi].push_back({op.x2, op.x2_off, op.x2_off + cw.C2});
                 wr[oi].push_back({op.out, op.out_off, op.out_off + cw.Cout});
-                if (op.out2 >= 0) wr[oi].push_back({op.out2, 0, cw.Cout});
                 int tile, split;
                 const auto& to = h->tensors[op.out];
                 conv_plan(B * to.H * to.W, cw.Cout, cw.Kpad, &tile, &split);
@@ -1181,7 +419,7 @@ int forward(fr_handle* h, const void* in, int in_fmt, int B, float* out, int fla
                     const auto& cw = h->convw[cv.wi];
                     const auto& to = h->tensors[cv.out];
                     if (stem_u8_supported(to.H, to.W, cv.cin, cw.K, cw.Kpad, cw.Cout, to.C, cv.out_off) && !cw.bias9 &&
-                        cv.res < 0 && cv.out2 < 0 && cv.sh == 1 && cv.ph == 1 && cv.kh == 3 && cv.kw == 3) {
+                        cv.res < 0 && cv.sh == 1 && cv.ph == 1 && cv.kh == 3 && cv.kw == 3) {
                         ps.flops = 2.0 * B * to.H * to.W * cw.Cout * 27.0;
                         ps.bytes = (double)B * to.H * to.W * (3.0 + cw.Cout * 2.0);
                         ps.start("stem u8 fused");
@@ -1352,7 +590,7 @@ int fr_load_weights(fr_handle* h, const void* blob, size_t nbytes) {
     if (!h || !blob) { set_error("fr_load_weights: null argument"); return FR_ERR_ARG; }
     std::lock_guard<std::mutex> lk(h->mu);
     FR_HIP_CHECK(hipSetDevice(h->device));
-    std::unordered_map<std::string, HostT> W;
+    Blob W;
     int rc = parse_blob(blob, nbytes, W);
     if (rc) return rc;
     const int keep_batch = h->max_batch;
@@ -1363,23 +601,20 @@ int fr_load_weights(fr_handle* h, const void* blob, size_t nbytes) {
     h->loaded = false;
     h->ex_tensor = h->ex_conv = -1;
     h->cut_l4in = -1;
-    Builder b{h, W};
-    if (h->arch == FR_ARCH_IRESNET100) build_iresnet100(b);
-    else if (h->arch == FR_ARCH_RESNET50_ARCFACE) build_resnet50(b);
-    else build_irv1(b);
-    if (!b.rc) b.rc = pack_conv_weights(h);
+    rc = build_plan(h, W);
+    if (!rc) rc = pack_conv_weights(h);
     for (auto& op : h->ops) op.grp = op.stage;  // plan entries (stage_plan)
     // the tensors whose producers record amax: inputs of e4m3 convs that run per-conv (an fp8 stage
     // scales its own input; its member convs are its fallback when the stage does not run)
     h->need_amax.assign(h->tensors.size(), 0);
     for (const auto& op : h->ops)
         if (op.kind == OP_CONV && op.wi >= 0 && h->convw[op.wi].w8 && op.in_off == 0) h->need_amax[op.in] = 1;
-    if (b.rc) {
+    if (rc) {
         free_weights(h);
         h->tensors.clear();
         h->ops.clear();
         DevSerial::reg(h, false);
-        return b.rc;
+        return rc;
     }
     h->loaded = true;
     DevSerial::reg(h, std::any_of(h->stages.begin(), h->stages.end(), [](const StageRec& r) { return r.parts > 1; }));
@@ -1707,321 +942,6 @@ int fr_features_at(fr_handle* h, const void* in, int in_fmt, int B, int H, int W
     return FR_OK;
 }
 
-int fr_gallery_set(fr_handle* h, const float* G, int64_t N, int D, int64_t index_base, int g_on_device) {
-    if (!h || (!G && N > 0) || N < 0 || D <= 0 || D % 4 != 0 || N + index_base > INT32_MAX) {
-        set_error("fr_gallery_set: bad argument (D must be a multiple of 4, indices must fit int32)");
-        return FR_ERR_ARG;
-    }
-    std::lock_guard<std::mutex> lk(h->mu);
-    FR_HIP_CHECK(hipSetDevice(h->device));
-    if (h->gallery) { (void)hipFree(h->gallery); h->gallery = nullptr; }
-    if (h->g_hi) { (void)hipFree(h->g_hi); h->g_hi = nullptr; }
-    h->g_rows = 0;
-    h->g_cap = N;
-    if (N > 0) {
-        void* p = nullptr;
-        int rc = dev_alloc(&p, (size_t)N * D * sizeof(float));
-        if (rc) return rc;
-        h->gallery = (float*)p;
-        FR_HIP_CHECK(hipMemcpy(p, G, (size_t)N * D * sizeof(float),
-                               g_on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice));
-        FR_HIP_CHECK(launch_gallery_prepare(h->gallery, N, D, nullptr));
-        if (N >= h->x3_min_rows && D == 512) {  // bf16 hi/lo copy for the candidate pass (match_x3.hip)
-            int rc2 = dev_alloc((void**)&h->g_hi, x3_gallery_elems(N) * sizeof(bf16_t));
-            if (!rc2) FR_HIP_CHECK(hipMemset(h->g_hi, 0, x3_gallery_elems(N) * sizeof(bf16_t)));
-            if (!rc2 && !h->match_fb) {
-                rc2 = dev_alloc((void**)&h->match_fb, sizeof(int));
-                if (!rc2) FR_HIP_CHECK(hipMemset(h->match_fb, 0, sizeof(int)));
-            }
-            if (rc2) return rc2;
-            FR_HIP_CHECK(launch_split_x3(h->gallery, 0, N, h->g_hi, nullptr));
-        }
-        FR_HIP_CHECK(hipDeviceSynchronize());
-    }
-    h->g_rows = N;
-    h->g_dim = D;
-    h->g_base = index_base;
-    return FR_OK;
-}
-
-// Rows [row0, row0 + n) of the gallery from G (host or device): an in-place update of existing rows and/or an
-// append (row0 <= rows).  Only the written rows are prepared (norm rule) and, on the bf16x3 path, split;
-// appends grow the allocation geometrically, so n single-row appends cost O(n) row copies amortised
-// instead of a full re-upload each (a served gallery under add_to_db traffic).
-int fr_gallery_write(fr_handle* h, const float* G, int64_t row0, int64_t n, int D, int g_on_device) {
-    if (!h || !G || n <= 0 || row0 < 0 || D <= 0 || D % 4 != 0) {
-        set_error("fr_gallery_write: bad argument");
-        return FR_ERR_ARG;
-    }
-    std::lock_guard<std::mutex> lk(h->mu);
-    if (h->g_rows > 0 && D != h->g_dim) { set_error("fr_gallery_write: D differs from the gallery's"); return FR_ERR_ARG; }
-    if (row0 > h->g_rows) { set_error("fr_gallery_write: row0 past the end (appends must be contiguous)"); return FR_ERR_ARG; }
-    const int64_t rows = std::max(h->g_rows, row0 + n);
-    if (rows + h->g_base > INT32_MAX) { set_error("fr_gallery_write: indices must fit int32"); return FR_ERR_ARG; }
-    FR_HIP_CHECK(hipSetDevice(h->device));
-    // once split, a gallery stays on the bf16x3 path (match_locked takes it whenever g_hi exists), so every
-    // written row must be re-split even if FR_OPT_X3_MIN_ROWS was raised since
-    const bool x3 = (h->g_hi != nullptr || rows >= h->x3_min_rows) && D == 512;
-    if (rows > h->g_cap || !h->gallery) {  // grow: 2x, copy the old rows on the device
-        const int64_t cap = std::max<int64_t>(rows, std::max<int64_t>(2 * h->g_cap, 1024));
-        float* g = nullptr;
-        int rc = dev_alloc((void**)&g, (size_t)cap * D * sizeof(float));
-        if (rc) return rc;
-        if (h->g_rows > 0)
-            FR_HIP_CHECK(hipMemcpy(g, h->gallery, (size_t)h->g_rows * D * sizeof(float), hipMemcpyDeviceToDevice));
-        if (h->gallery) (void)hipFree(h->gallery);
-        h->gallery = g;
-        if (h->g_hi) { (void)hipFree(h->g_hi); h->g_hi = nullptr; }  // re-split below at the new capacity
-        h->g_cap = cap;
-    }
-    FR_HIP_CHECK(hipMemcpy(h->gallery + (size_t)row0 * D, G, (size_t)n * D * sizeof(float),
-                           g_on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice));
-    FR_HIP_CHECK(launch_gallery_prepare(h->gallery + (size_t)row0 * D, n, D, nullptr));
-    if (x3) {
-        int64_t s0 = row0, sn = n;
-        if (!h->g_hi) {  // first time on the bf16x3 path (or re-grown): split every row
-            int rc = dev_alloc((void**)&h->g_hi, x3_gallery_elems(h->g_cap) * sizeof(bf16_t));
-            if (!rc) FR_HIP_CHECK(hipMemset(h->g_hi, 0, x3_gallery_elems(h->g_cap) * sizeof(bf16_t)));
-            if (!rc && !h->match_fb) {
-                rc = dev_alloc((void**)&h->match_fb, sizeof(int));
-                if (!rc) FR_HIP_CHECK(hipMemset(h->match_fb, 0, sizeof(int)));
-            }
-            if (rc) return rc;
-            s0 = 0;
-            sn = rows;
-        }
-        FR_HIP_CHECK(launch_split_x3(h->gallery, s0, sn, h->g_hi, nullptr));
-    }
-    FR_HIP_CHECK(hipDeviceSynchronize());
-    h->g_rows = rows;
-    h->g_dim = D;
-    return FR_OK;
-}
-
-int64_t fr_gallery_rows(const fr_handle* h) { return h ? h->g_rows : 0; }
-
-static int ensure_cand(fr_handle* h, size_t need) {
-    if (need <= h->cand_cap) return FR_OK;
-    if (h->cand_s) (void)hipFree(h->cand_s);
-    if (h->cand_i) (void)hipFree(h->cand_i);
-    h->cand_s = nullptr;
-    h->cand_i = nullptr;
-    h->cand_cap = 0;
-    int rc = dev_alloc((void**)&h->cand_s, need * sizeof(float));
-    if (rc) return rc;
-    rc = dev_alloc((void**)&h->cand_i, need * sizeof(int32_t));
-    if (rc) return rc;
-    h->cand_cap = need;
-    return FR_OK;
-}
-
-// FR_AB no_match_rows: small batches take the MFMA match kernels too (A/B timing)
-static bool match_rows_enabled() {
-    static const bool on = [] { return !ab_int("no_match_rows", 0); }();
-    return on;
-}
-
-static int match_locked(fr_handle* h, const float* P, int B, int k, float* scores, int32_t* idx, void* stream) {
-    if (!P || !scores || !idx || B <= 0 || k <= 0 || k > FR_TOPK_LARGE_MAX) {
-        set_error("fr_match_topk: bad argument (1 <= k <= " + std::to_string(FR_TOPK_LARGE_MAX) + ")");
-        return FR_ERR_ARG;
-    }
-    if (!h->gallery || h->g_rows <= 0) { set_error("fr_match_topk: no gallery"); return FR_ERR_STATE; }
-    FR_HIP_CHECK(hipSetDevice(h->device));
-    hipStream_t s = (hipStream_t)stream;
-    if (k > 16) {  // exact score rows in stream-ordered scratch, <= 256 MiB per probe chunk, + radix select
-        if (h->g_rows > 0x7fffffff) { set_error("fr_match_topk: k > 16 needs a gallery below 2^31 rows"); return FR_ERR_ARG; }
-        const int chunk = (int)std::max<int64_t>(1, std::min<int64_t>(B, ((int64_t)1 << 26) / h->g_rows));
-        float* S = nullptr;
-        FR_HIP_CHECK(hipMallocAsync((void**)&S, (size_t)chunk * h->g_rows * sizeof(float), s));
-        for (int b0 = 0; b0 < B; b0 += chunk) {
-            const int nb = std::min(chunk, B - b0);
-            const hipError_t e = launch_match_topk_large(P + (size_t)b0 * h->g_dim, nb, h->gallery, h->g_rows, h->g_dim, k,
-                                                         h->g_base, S, scores + (size_t)b0 * k, idx + (size_t)b0 * k, s);
-            if (e != hipSuccess) {
-                (void)hipFreeAsync(S, s);
-                FR_HIP_CHECK(e);
-            }
-        }
-        FR_HIP_CHECK(hipFreeAsync(S, s));
-        return FR_OK;
-    }
-    int n_split;
-    int64_t rps;
-    // B <= 4 (the online bs = 1 path): one wave per 64 rows, exact f32 scores in the f32 kernels' order
-    if (match_rows_enabled() && match_rows_supported(B, h->g_dim, k)) {
-        int n_lists, R;
-        match_rows_plan(h->g_rows, &n_lists, &R);
-        int rc = ensure_cand(h, (size_t)B * n_lists * k);
-        if (rc) return rc;
-        FR_HIP_CHECK(launch_match_rows(P, B, h->gallery, h->g_rows, h->g_dim, k, h->g_base, h->cand_s, h->cand_i,
-                                       n_lists, R, s));
-        FR_HIP_CHECK(launch_topk_merge(h->cand_s, h->cand_i, B, n_lists, k, scores, idx, s));
-        return FR_OK;
-    }
-    // bf16x3 candidates + exact f32 rescoring (match_x3.hip).  Its proof needs the k-th exact score to
-    // clear the 16th candidate by 2 eps, which a k close to 16 almost never does (every probe would be
-    // rescanned by one wave), so k > 8 takes the exact kernel.
-    if (h->g_hi && !h->match_exact && 2 * k <= match_x3_candidates()) {
-        match_x3_plan(B, h->g_rows, &n_split, &rps);
-        int rc = ensure_cand(h, (size_t)B * n_split * match_x3_candidates());
-        if (rc) return rc;
-        FR_HIP_CHECK(launch_match_x3(P, B, h->gallery, h->g_hi, h->g_rows, h->g_dim, k, h->g_base, h->cand_s,
-                                     h->cand_i, n_split, rps, scores, idx, h->match_fb, s));
-        return FR_OK;
-    }
-    match_split_plan(B, h->g_rows, h->g_dim, k, &n_split, &rps);
-    int rc = ensure_cand(h, (size_t)B * n_split * k);
-    if (rc) return rc;
-    FR_HIP_CHECK(launch_match_topk(P, B, h->gallery, h->g_rows, h->g_dim, k, h->g_base, h->cand_s, h->cand_i,
-                                   n_split, rps, s));
-    FR_HIP_CHECK(launch_topk_merge(h->cand_s, h->cand_i, B, n_split, k, scores, idx, s));
-    return FR_OK;
-}
-
-int fr_match_topk(fr_handle* h, const float* P, int B, int k, float* scores, int32_t* idx, void* stream) {
-    if (!h) { set_error("fr_match_topk: null handle"); return FR_ERR_ARG; }
-    std::lock_guard<std::mutex> lk(h->mu);
-    return match_locked(h, P, B, k, scores, idx, stream);
-}
-
-int fr_match_eval(fr_handle* h, const float* P, int B, const int32_t* true_idx, int k, float* scores, int32_t* idx,
-                  float* true_score, int32_t* true_rank, uint64_t* hist, int nbins, float lo, float hi, void* stream) {
-    const bool want_topk = k != 0;  // k = 0: scores / idx are not written (and may be NULL)
-    if (!P || !true_idx || !true_score || !true_rank || B <= 0) {
-        set_error("fr_match_eval: bad argument (P, true_idx, true_score, true_rank must be set, B >= 1)");
-        return FR_ERR_ARG;
-    }
-    if (want_topk && (k <= 0 || !scores || !idx)) {
-        set_error("fr_match_eval: bad argument (k >= 1 with scores and idx, or k = 0 for no top-k)");
-        return FR_ERR_ARG;
-    }
-    if (hist && (nbins < 1 || nbins > 2048 || !(hi > lo))) {
-        set_error("fr_match_eval: bad argument (1 <= nbins <= 2048 and hi > lo with a histogram)");
-        return FR_ERR_ARG;
-    }
-    if (!h) { set_error("fr_match_eval: null handle"); return FR_ERR_ARG; }
-    std::lock_guard<std::mutex> lk(h->mu);
-    if (!h->gallery || h->g_rows <= 0) { set_error("fr_match_eval: no gallery"); return FR_ERR_STATE; }
-    if (h->g_rows > 0x7fffffff) { set_error("fr_match_eval: needs a gallery below 2^31 rows"); return FR_ERR_ARG; }
-    if (want_topk) {  // fr_match_topk's launches, unchanged
-        int rc = match_locked(h, P, B, k, scores, idx, stream);
-        if (rc) return rc;
-    }
-    FR_HIP_CHECK(hipSetDevice(h->device));
-    const float inv_w = hist ? (float)nbins / (hi - lo) : 0.f;  // rounded once, here
-    FR_HIP_CHECK(launch_match_eval(P, B, h->gallery, h->g_rows, h->g_dim, h->g_base, true_idx, true_score, true_rank,
-                                   (unsigned long long*)hist, nbins, lo, inv_w, (hipStream_t)stream));
-    return FR_OK;
-}
-
-int fr_debug_match_eval_splits(fr_handle* h, int B) {
-    if (!h || B <= 0) { set_error("fr_debug_match_eval_splits: bad argument"); return FR_ERR_ARG; }
-    std::lock_guard<std::mutex> lk(h->mu);
-    if (!h->gallery || h->g_rows <= 0) { set_error("fr_debug_match_eval_splits: no gallery"); return FR_ERR_STATE; }
-    int n_split;
-    int64_t rps;
-    match_eval_plan(B, h->g_rows, h->g_dim, &n_split, &rps);
-    return n_split;
-}
-
-size_t fr_match_range_workspace(const fr_handle* h, int B) {
-    if (!h || B <= 0) { set_error("fr_match_range_workspace: bad argument"); return 0; }
-    fr_handle* hm = const_cast<fr_handle*>(h);
-    std::lock_guard<std::mutex> lk(hm->mu);
-    if (!h->gallery || h->g_rows <= 0) { set_error("fr_match_range_workspace: no gallery"); return 0; }
-    const size_t n = match_range_workspace(B, h->g_rows, h->g_dim);
-    if (!n) set_error("fr_match_range_workspace: needs a gallery below 2^31 rows");
-    return n;
-}
-
-// The checks fr_match_range_count and fr_match_range_fill share, past their own pointer arguments.
-static int range_state_check(fr_handle* h, const char* who) {
-    if (!h->gallery || h->g_rows <= 0) { set_error(std::string(who) + ": no gallery"); return FR_ERR_STATE; }
-    if (h->g_rows > 0x7fffffff) { set_error(std::string(who) + ": needs a gallery below 2^31 rows"); return FR_ERR_ARG; }
-    return FR_OK;
-}
-
-int fr_match_range_count(fr_handle* h, const float* P, int B, float thresh, const int32_t* after, void* ws,
-                         int64_t* lims, void* stream) {
-    if (!P || !ws || !lims || B <= 0 || std::isnan(thresh)) {
-        set_error("fr_match_range_count: bad argument (P, ws, lims must be set, B >= 1, thresh not NaN)");
-        return FR_ERR_ARG;
-    }
-    if (!h) { set_error("fr_match_range_count: null handle"); return FR_ERR_ARG; }
-    std::lock_guard<std::mutex> lk(h->mu);
-    if (int rc = range_state_check(h, "fr_match_range_count")) return rc;
-    FR_HIP_CHECK(hipSetDevice(h->device));
-    FR_HIP_CHECK(launch_match_range_count(P, B, h->gallery, h->g_rows, h->g_dim, h->g_base, thresh, after, (int32_t*)ws,
-                                          lims, (hipStream_t)stream));
-    return FR_OK;
-}
-
-int fr_match_range_fill(fr_handle* h, const float* P, int B, float thresh, const int32_t* after, const void* ws,
-                        const int64_t* lims, float* scores, int32_t* idx, int64_t capacity, void* stream) {
-    if (!P || !ws || !lims || !scores || !idx || B <= 0 || std::isnan(thresh) || capacity < 0) {
-        set_error("fr_match_range_fill: bad argument (P, ws, lims, scores, idx must be set, B >= 1, thresh not NaN, "
-                  "capacity >= 0)");
-        return FR_ERR_ARG;
-    }
-    if (!h) { set_error("fr_match_range_fill: null handle"); return FR_ERR_ARG; }
-    std::lock_guard<std::mutex> lk(h->mu);
-    if (int rc = range_state_check(h, "fr_match_range_fill")) return rc;
-    FR_HIP_CHECK(hipSetDevice(h->device));
-    FR_HIP_CHECK(launch_match_range_fill(P, B, h->gallery, h->g_rows, h->g_dim, h->g_base, thresh, after,
-                                         (const int32_t*)ws, lims, scores, idx, capacity, (hipStream_t)stream));
-    return FR_OK;
-}
-
-int fr_debug_match_range_splits(fr_handle* h, int B) {
-    if (!h || B <= 0) { set_error("fr_debug_match_range_splits: bad argument"); return FR_ERR_ARG; }
-    std::lock_guard<std::mutex> lk(h->mu);
-    if (!h->gallery || h->g_rows <= 0) { set_error("fr_debug_match_range_splits: no gallery"); return FR_ERR_STATE; }
-    int n_split;
-    int64_t rps;
-    match_range_plan(B, h->g_rows, h->g_dim, &n_split, &rps);
-    return n_split;
-}
-
-int fr_gallery_read(const fr_handle* h, int64_t row0, int64_t n, float* out, int out_on_device) {
-    if (row0 < 0 || n < 0 || (!out && n > 0)) {
-        set_error("fr_gallery_read: bad argument (row0 >= 0, n >= 0, out must be set)");
-        return FR_ERR_ARG;
-    }
-    if (!h) { set_error("fr_gallery_read: null handle"); return FR_ERR_ARG; }
-    fr_handle* hm = const_cast<fr_handle*>(h);
-    std::lock_guard<std::mutex> lk(hm->mu);
-    if (row0 > h->g_rows || n > h->g_rows - row0) {
-        set_error("fr_gallery_read: rows [" + std::to_string(row0) + ", " + std::to_string(row0) + " + " +
-                  std::to_string(n) + ") outside a gallery of " + std::to_string(h->g_rows) + " rows");
-        return FR_ERR_ARG;
-    }
-    if (n == 0) return FR_OK;
-    FR_HIP_CHECK(hipSetDevice(h->device));
-    FR_HIP_CHECK(hipMemcpy(out, h->gallery + (size_t)row0 * h->g_dim, (size_t)n * h->g_dim * sizeof(float),
-                           out_on_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost));
-    return FR_OK;
-}
-
-int fr_topk_merge(const float* cand_s, const int32_t* cand_i, int B, int n_lists, int k, float* scores,
-                  int32_t* idx, void* stream) {
-    if (!cand_s || !cand_i || !scores || !idx || B <= 0 || n_lists <= 0 || k <= 0 || k > 16) {
-        set_error("fr_topk_merge: bad argument");
-        return FR_ERR_ARG;
-    }
-    FR_HIP_CHECK(launch_topk_merge(cand_s, cand_i, B, n_lists, k, scores, idx, (hipStream_t)stream));
-    return FR_OK;
-}
-
-int fr_topk_merge_ranks(const void* xchg, int n_ranks, int B, int k, float* scores, int32_t* idx, void* stream) {
-    if (!xchg || !scores || !idx || B <= 0 || n_ranks <= 0 || k <= 0 || k > 16) {
-        set_error("fr_topk_merge_ranks: bad argument");
-        return FR_ERR_ARG;
-    }
-    FR_HIP_CHECK(launch_topk_merge_ranks(xchg, n_ranks, B, k, scores, idx, (hipStream_t)stream));
-    return FR_OK;
-}
-
 int fr_embed_match(fr_handle* h, const void* in, int in_fmt, int B, int H, int W, int k, float* emb_out,
                    float* scores, int32_t* idx, void* stream) {
     if (!h) { set_error("fr_embed_match: null handle"); return FR_ERR_ARG; }
@@ -2120,17 +1040,6 @@ int fr_get_option(const fr_handle* h, int option) {
         case FR_OPT_FUSED_MASK: return h->fused_mask;
         default: return FR_ERR_ARG;
     }
-}
-
-int fr_debug_match_fallbacks(fr_handle* h) {
-    if (!h) return FR_ERR_ARG;
-    std::lock_guard<std::mutex> lk(h->mu);
-    if (!h->match_fb) return 0;
-    int v = 0;
-    FR_HIP_CHECK(hipSetDevice(h->device));
-    FR_HIP_CHECK(hipDeviceSynchronize());
-    FR_HIP_CHECK(hipMemcpy(&v, h->match_fb, sizeof(int), hipMemcpyDeviceToHost));
-    return v;
 }
 
 int fr_debug_stage_timeouts(fr_handle* h) {
@@ -2315,310 +1224,6 @@ int fr_debug_copy_tensor(fr_handle* h, int t, int B, void* dst, void* stream) {
     const auto& d = h->tensors[t];
     FR_HIP_CHECK(hipMemcpyAsync(dst, d.dev, (size_t)B * d.H * d.W * d.C * sizeof(bf16_t), hipMemcpyDeviceToDevice,
                                 (hipStream_t)stream));
-    return FR_OK;
-}
-
-int fr_op_conv2d(const fr_conv_desc* d, void* stream) { return fr_op_conv2d_ex(d, nullptr, stream); }
-
-int fr_op_conv2d_ex(const fr_conv_desc* d, const fr_conv_ext* e, void* stream) {
-    if (!d || !d->x || !d->w || !d->y || d->B <= 0 || d->Cin <= 0 || d->Cin % 8 || d->Cx % 8 || d->x_off % 8 ||
-        d->Cout <= 0 || d->Cout % 8 || d->Cy % 8 || d->y_off % 8 || d->Npad % 128 || d->Kpad % 64 ||
-        d->Npad < d->Cout || d->Kpad < d->Kh * d->Kw * d->Cin || d->x_off + d->Cin > d->Cx ||
-        d->y_off + d->Cout > d->Cy || (d->act == 2 && !d->slope) || (d->res && (d->Cres % 8 || d->res_off % 8)) ||
-        (d->y2 && (!d->aff_s || !d->aff_b || d->Cy2 % 8 || d->y2_off % 8)) || d->stride_h <= 0 || d->stride_w <= 0) {
-        set_error("fr_op_conv2d: bad descriptor (see alignment rules in frhip.h)");
-        return FR_ERR_ARG;
-    }
-    ConvArgs a{};
-    a.x = (const bf16_t*)d->x; a.B = d->B; a.H = d->H; a.W = d->W; a.Cx = d->Cx; a.x_off = d->x_off; a.Cin = d->Cin;
-    a.w = (const bf16_t*)d->w; a.Kh = d->Kh; a.Kw = d->Kw; a.sh = d->stride_h; a.sw = d->stride_w;
-    a.ph = d->pad_h; a.pw = d->pad_w; a.K = d->Kh * d->Kw * d->Cin; a.Kpad = d->Kpad;
-    a.Ho = d->Ho ? d->Ho : (d->H + 2 * d->pad_h - d->Kh) / d->stride_h + 1;
-    a.Wo = d->Wo ? d->Wo : (d->W + 2 * d->pad_w - d->Kw) / d->stride_w + 1;
-    a.M = d->B * a.Ho * a.Wo; a.Cout = d->Cout; a.Npad = d->Npad;
-    a.bias = d->bias; a.slope = d->slope; a.act = d->act; a.bias9 = d->bias9;
-    a.res = (const bf16_t*)d->res; a.Cres = d->Cres; a.res_off = d->res_off;
-    a.y = (bf16_t*)d->y; a.Cy = d->Cy; a.y_off = d->y_off;
-    a.y2 = (bf16_t*)d->y2; a.Cy2 = d->Cy2; a.y2_off = d->y2_off; a.aff_s = d->aff_s; a.aff_b = d->aff_b;
-    a.f16 = d->dtype == FR_DTYPE_F16;
-    a.y_amax = d->y_amax;
-    a.amax_slots = 1;
-    int* splitk_cnt = nullptr;
-    if (e) {
-        // every refusal is made here, on the host, before any launch: a kernel that cannot run a field never sees it
-        const auto refuse = [](const char* why) {
-            set_error(std::string("fr_op_conv2d_ex: ") + why);
-            return FR_ERR_ARG;
-        };
-        const int tile = d->tile;  // its kernel takes a field or not: convs.cpp's table
-        const int takes = op_tile_takes(tile);
-        if (e->amax_slots < 0) return refuse("amax_slots < 0");
-        if (e->amax_slots > 0) a.amax_slots = e->amax_slots;
-        if (e->x2) {
-            if (d->dtype == FR_DTYPE_FP8) return refuse("the K-concatenated projection (x2) has no fp8 kernel");
-            if (!(takes & CONV_TAKES_X2))
-                return refuse(("the K-concatenated projection (x2) runs only on " + conv_takers(CONV_TAKES_X2)).c_str());
-            if (e->st2 <= 0 || e->H2 <= 0 || e->W2 <= 0 || e->C2 <= 0 || e->x2_off < 0 || e->Cx2 % 8 || e->x2_off % 8 ||
-                d->Cin % 64 || e->C2 % 64 || a.K + e->C2 > d->Kpad || e->x2_off + e->C2 > e->Cx2 ||
-                (a.Ho - 1) * e->st2 >= e->H2 || (a.Wo - 1) * e->st2 >= e->W2)
-                return refuse("bad projection (x2): needs Cin % 64 == 0, C2 % 64 == 0, Kh*Kw*Cin + C2 <= Kpad, "
-                              "x2_off + C2 <= Cx2, Cx2 % 8 == 0, x2_off % 8 == 0, (Ho-1)*st2 < H2, (Wo-1)*st2 < W2");
-            a.x2 = (const bf16_t*)e->x2; a.H2 = e->H2; a.W2 = e->W2; a.Cx2 = e->Cx2; a.x2_off = e->x2_off;
-            a.C2 = e->C2; a.st2 = e->st2; a.K1 = a.K;
-            a.K = a.K1 + a.C2;
-        }
-        if (e->y_bf16) {
-            if (d->dtype != FR_DTYPE_F16 || d->res || d->y2) return refuse("y_bf16 needs FR_DTYPE_F16 and neither res nor y2");
-            if (!(takes & CONV_TAKES_Y_BF16)) return refuse(("y_bf16 runs only on " + conv_takers(CONV_TAKES_Y_BF16)).c_str());
-            a.y_bf16 = 1;
-        }
-        if (e->splitk_cnt) {
-            if (!(takes & CONV_TAKES_SPLITK_CNT) || d->dtype == FR_DTYPE_FP8) return refuse("splitk_cnt (in-launch split-K) is for the implicit-GEMM tiles only");
-            // (the in-launch slabs are addressed by 32-bit buffer offsets)
-            if (d->split_k > 1 && (size_t)d->split_k * a.M * a.Npad * sizeof(float) >= 0x7fffffffull)
-                return refuse("splitk_cnt: the partial workspace must stay below 2 GiB");
-            splitk_cnt = e->splitk_cnt;
-        }
-    }
-    if (d->dtype == FR_DTYPE_FP8) {
-        if (!d->wscale || !d->x_amax || d->Cin % 64 || d->Kpad % 128 || d->split_k > 1) {
-            set_error("fr_op_conv2d: fp8 needs wscale, x_amax, Cin % 64 == 0, Kpad % 128 == 0, no split-K");
-            return FR_ERR_ARG;
-        }
-        a.w8 = (const uint8_t*)d->w; a.wscale = d->wscale; a.x_amax = d->x_amax;
-        a.tile = conv_fp8_tile(a.M, a.Cout);
-        if (d->tile > 0) {  // conv_fp8.hip has three tiles; any other id would run the 128x128 one under a wrong name
-            a.tile = d->tile - 1;
-            if (a.tile != TILE_128x128 && a.tile != TILE_128x64 && a.tile != TILE_64x128) {
-                set_error("fr_op_conv2d: fp8 runs on FR_TILE_128x128, FR_TILE_128x64 and FR_TILE_64x128 only");
-                return FR_ERR_ARG;
-            }
-        }
-        FR_HIP_CHECK(launch_conv_fp8(a, (hipStream_t)stream));
-        return FR_OK;
-    }
-    if (op_tile_forced_kind(d->tile))  // a specialised kernel (split_k: its own split, conv_small.hip's KS | NF << 8)
-        return run_forced_kind(d->tile, a, d->split_k > 1 ? d->split_k : 1, (hipStream_t)stream);
-    if (d->tile > 0) {
-        if (!op_tile_is_igemm(d->tile)) {
-            set_error("fr_op_conv2d: bad tile");
-            return FR_ERR_ARG;
-        }
-        a.tile = d->tile - 1;
-    } else {
-        int tile, sp;
-        conv_plan(a.M, a.Cout, a.Kpad, &tile, &sp);
-        a.tile = tile;
-    }
-    if (d->split_k > 1) {
-        if (!d->partial) { set_error("fr_op_conv2d: split_k > 1 needs partial workspace"); return FR_ERR_ARG; }
-        a.split_k = d->split_k;
-        a.partial = d->partial;
-        a.splitk_cnt = splitk_cnt;  // non-null: the tiles' last workgroups reduce, no second launch
-        FR_HIP_CHECK(launch_conv(a, (hipStream_t)stream));
-        if (!a.splitk_cnt) FR_HIP_CHECK(launch_splitk_epilogue(a, (hipStream_t)stream));
-    } else {
-        a.split_k = 1;
-        FR_HIP_CHECK(launch_conv(a, (hipStream_t)stream));
-    }
-    return FR_OK;
-}
-
-size_t fr_resize_u8_workspace(int B, int H, int W, int OH, int OW) {
-    if (B <= 0 || H <= 0 || W <= 0 || OH <= 0 || OW <= 0) return 0;
-    return resize_u8_workspace(B, H, W, OH, OW);
-}
-
-int fr_resize_u8(const uint8_t* in, int B, int H, int W, uint8_t* out, int OH, int OW, void* ws, size_t ws_bytes,
-                 void* stream) {
-    if (!in || !out || B <= 0 || H <= 0 || W <= 0 || OH <= 0 || OW <= 0 || (size_t)B * H * W * 3 > 0x7fffffffull * 4) {
-        set_error("fr_resize_u8: bad argument");
-        return FR_ERR_ARG;
-    }
-    if (ws_bytes < resize_u8_workspace(B, H, W, OH, OW) || (!ws && ws_bytes == 0 && W != OW)) {
-        set_error("fr_resize_u8: workspace smaller than fr_resize_u8_workspace()");
-        return FR_ERR_ARG;
-    }
-    FR_HIP_CHECK(launch_resize_u8(in, B, H, W, out, OH, OW, ws, (hipStream_t)stream));
-    return FR_OK;
-}
-
-int fr_warp_affine_u8(const uint8_t* in, int B, int H, int W, const double* M, uint8_t* out, int OH, int OW,
-                      void* stream) {
-    if (!in || !out || !M || B <= 0 || H <= 0 || W <= 0 || OH <= 0 || OW <= 0) {
-        set_error("fr_warp_affine_u8: bad argument");
-        return FR_ERR_ARG;
-    }
-    FR_HIP_CHECK(launch_warp_affine_u8(in, B, H, W, M, out, OH, OW, (hipStream_t)stream));
-    return FR_OK;
-}
-
-int fr_op_preprocess(const void* in, int in_fmt, int B, int H, int W, void* out, int dtype, void* stream) {
-    if (!in || !out || B <= 0 || H <= 0 || W <= 0 || (in_fmt != FR_IN_U8_NHWC && in_fmt != FR_IN_F32_NCHW)) {
-        set_error("fr_op_preprocess: bad argument");
-        return FR_ERR_ARG;
-    }
-    FR_HIP_CHECK(launch_preprocess(in, in_fmt, B, H, W, (bf16_t*)out, dtype == FR_DTYPE_F16, (hipStream_t)stream));
-    return FR_OK;
-}
-
-int fr_op_maxpool(const void* x, int B, int H, int W, int Cx, int x_off, int C, int k, int stride, int pad, void* y,
-                  int Cy, int y_off, int Ho, int Wo, int dtype, void* stream) {
-    if (!x || !y || C % 8 || Cx % 8 || x_off % 8 || Cy % 8 || y_off % 8 || k <= 0 || stride <= 0 || pad < 0 ||
-        pad >= k) {
-        set_error("fr_op_maxpool: bad argument");
-        return FR_ERR_ARG;
-    }
-    FR_HIP_CHECK(launch_maxpool((const bf16_t*)x, B, H, W, Cx, x_off, C, k, stride, pad, (bf16_t*)y, Cy, y_off, Ho,
-                                Wo, dtype == FR_DTYPE_F16, (hipStream_t)stream));
-    return FR_OK;
-}
-
-int fr_op_avgpool(const void* x, int B, int H, int W, int C, void* y, int dtype, void* stream) {
-    if (!x || !y || C % 8) { set_error("fr_op_avgpool: bad argument"); return FR_ERR_ARG; }
-    FR_HIP_CHECK(launch_avgpool((const bf16_t*)x, B, H, W, C, (bf16_t*)y, dtype == FR_DTYPE_F16, (hipStream_t)stream));
-    return FR_OK;
-}
-
-int fr_op_linear(const void* x, int B, int K, const void* w, int N, int Npad, int Kpad, const float* bias,
-                 int normalize, float* out, int split_k, float* partial, int dtype, void* stream) {
-    if (!x || !w || !out || !partial || B <= 0 || K <= 0 || K % 8 || N <= 0 || N % 8 || Npad % 128 || Kpad % 64 ||
-        Npad < N || Kpad < K || split_k <= 0) {
-        set_error("fr_op_linear: bad argument");
-        return FR_ERR_ARG;
-    }
-    ConvArgs a{};
-    a.x = (const bf16_t*)x; a.B = B; a.H = 1; a.W = 1; a.Cx = K; a.x_off = 0; a.Cin = K;
-    a.w = (const bf16_t*)w; a.Kh = 1; a.Kw = 1; a.sh = 1; a.sw = 1; a.K = K; a.Kpad = Kpad;
-    a.Ho = 1; a.Wo = 1; a.M = B; a.Cout = N; a.Npad = Npad;
-    a.split_k = split_k;
-    a.partial = partial;
-    a.f16 = dtype == FR_DTYPE_F16;
-    {
-        int tile, sp;
-        conv_plan(a.M, a.Cout, a.Kpad, &tile, &sp);
-        a.tile = tile;
-    }
-    FR_HIP_CHECK(launch_conv(a, (hipStream_t)stream));
-    FR_HIP_CHECK(launch_head_finalize(partial, split_k, B, N, Npad, bias, normalize, out, (hipStream_t)stream));
-    return FR_OK;
-}
-
-int fr_op_head_gemv(const void* x, int B, int K, const void* w, int N, int Npad, int Kpad, const float* bias,
-                    int normalize, float* out, int S, float* partial, int dtype, void* stream) {
-    if (!x || !w || !out || !partial || K <= 0 || N <= 0 || Npad < N || S < 1 || Kpad % 8 || N % 4 || N > 1024 ||
-        (dtype != FR_DTYPE_BF16 && dtype != FR_DTYPE_F16) || !head_gemv_supported(B, K, Kpad, Npad)) {
-        set_error("fr_op_head_gemv: bad argument (1 <= B <= 8, K % 8 == 0, Kpad % 8 == 0, Kpad >= K, Npad % 16 == 0, "
-                  "N % 4 == 0, N <= 1024, S >= 1, bf16 / f16)");
-        return FR_ERR_ARG;
-    }
-    FR_HIP_CHECK(launch_head_gemv((const bf16_t*)x, B, K, (const bf16_t*)w, Kpad, N, Npad, S, dtype == FR_DTYPE_F16,
-                                  partial, (hipStream_t)stream));
-    FR_HIP_CHECK(launch_head_finalize(partial, S, B, N, Npad, bias, normalize, out, (hipStream_t)stream));
-    return FR_OK;
-}
-
-int fr_op_head_grad(const float* g, int B, int N, const void* w, int K, int Kpad, int dtype, float* v, void* stream) {
-    if (!g || !w || !v || (dtype != FR_DTYPE_BF16 && dtype != FR_DTYPE_F16) || !head_grad_supported(B, N, K, Kpad)) {
-        set_error("fr_op_head_grad: bad argument (B >= 1, 1 <= N <= 1024, K % 8 == 0, Kpad % 8 == 0, Kpad >= K, bf16 / f16)");
-        return FR_ERR_ARG;
-    }
-    FR_HIP_CHECK(launch_head_grad(g, B, N, (const bf16_t*)w, K, Kpad, dtype == FR_DTYPE_F16, v, (hipStream_t)stream));
-    return FR_OK;
-}
-
-int fr_op_cam(const void* act, int B, int h, int w, int C, int dtype, const float* v, int v_layout, int S, float* cam,
-              float* low, void* stream) {
-    if (!act || !cam || (dtype != FR_DTYPE_BF16 && dtype != FR_DTYPE_F16) || v_layout < 0 || v_layout > 2 ||
-        (v_layout != 2 && !v) || !cam_supported(B, h, w, C, S)) {
-        set_error("fr_op_cam: bad argument (h * w <= 256, C % 8 == 0, C <= 4096, 1 <= S <= 4096, v_layout 0 / 1 with v, "
-                  "2 without, bf16 / f16)");
-        return FR_ERR_ARG;
-    }
-    FR_HIP_CHECK(launch_cam((const bf16_t*)act, B, h, w, C, dtype == FR_DTYPE_F16, v, v_layout == 0 ? C : h * w * C,
-                            v_layout, S, cam, low, (hipStream_t)stream));
-    return FR_OK;
-}
-
-int fr_op_proj_l2(const float* x, int B, int K, const float* W, const float* bias, int N, int normalize, float* out,
-                  void* stream) {
-    if (!x || !W || !out || B <= 0 || K <= 0 || K > 1024 || N <= 0) {
-        set_error("fr_op_proj_l2: bad argument (1 <= K <= 1024)");
-        return FR_ERR_ARG;
-    }
-    FR_HIP_CHECK(launch_proj_l2(x, B, K, W, bias, N, normalize, out, (hipStream_t)stream));
-    return FR_OK;
-}
-
-int fr_op_l2norm_rows(float* x, int B, int D, void* stream) {
-    if (!x || B <= 0 || D <= 0) { set_error("fr_op_l2norm_rows: bad argument"); return FR_ERR_ARG; }
-    FR_HIP_CHECK(launch_l2norm_rows(x, B, D, (hipStream_t)stream));
-    return FR_OK;
-}
-
-int fr_op_amax(const void* x, size_t n, int dtype, float* amax, int slots, void* stream) {
-    if (!x || !amax || n == 0 || n % 8 || slots < 1 || (dtype != FR_DTYPE_BF16 && dtype != FR_DTYPE_F16)) {
-        set_error("fr_op_amax: bad argument (n % 8 == 0, slots >= 1, bf16 / f16)");
-        return FR_ERR_ARG;
-    }
-    FR_HIP_CHECK(launch_amax((const bf16_t*)x, n, dtype == FR_DTYPE_F16, amax, slots, (hipStream_t)stream));
-    return FR_OK;
-}
-
-int fr_op_maxpool_cvt(const void* x, int B, int H, int W, int Cx, int x_off, int C, int k, int stride, int pad, void* y,
-                      int Cy, int y_off, int Ho, int Wo, void* stream) {
-    if (!x || !y || B <= 0 || C <= 0 || C % 8 || Cx % 8 || x_off % 8 || Cy % 8 || y_off % 8 || k != 3 || stride <= 0 ||
-        pad < 0 || pad >= k) {
-        set_error("fr_op_maxpool_cvt: bad argument (the f16 -> bf16 pool is 3x3 only)");
-        return FR_ERR_ARG;
-    }
-    FR_HIP_CHECK(launch_maxpool((const bf16_t*)x, B, H, W, Cx, x_off, C, k, stride, pad, (bf16_t*)y, Cy, y_off, Ho, Wo, 1,
-                                (hipStream_t)stream, 1));
-    return FR_OK;
-}
-
-/* ---- MTCNN face detector building blocks (mtcnn.hip) ---- */
-int fr_area_resample_u8(const uint8_t* img, int H, int W, const int32_t* regions, int n, int oh, int ow, float* out,
-                        void* stream) {
-    if (!img || !regions || !out || H <= 0 || W <= 0 || n <= 0 || oh <= 0 || ow <= 0) {
-        set_error("fr_area_resample_u8: bad argument");
-        return FR_ERR_ARG;
-    }
-    FR_HIP_CHECK(launch_area_resample(img, H, W, regions, n, oh, ow, out, (hipStream_t)stream));
-    return FR_OK;
-}
-
-int fr_mtcnn_conv(const float* x, int B, int H, int W, int Cin, const float* w, const float* bias, const float* slope,
-                  int Cout, int kh, int kw, float* y, void* stream) {
-    if (!x || !w || !y || B <= 0 || Cin <= 0 || Cout <= 0 || kh <= 0 || kw <= 0 || H < kh || W < kw) {
-        set_error("fr_mtcnn_conv: bad argument");
-        return FR_ERR_ARG;
-    }
-    FR_HIP_CHECK(launch_mtcnn_conv(x, B, H, W, Cin, w, bias, slope, Cout, kh, kw, y, (hipStream_t)stream));
-    return FR_OK;
-}
-
-int fr_mtcnn_maxpool(const float* x, int B, int H, int W, int C, int k, int stride, float* y, void* stream) {
-    if (!x || !y || B <= 0 || C <= 0 || k <= 0 || stride <= 0 || H < 1 || W < 1) {
-        set_error("fr_mtcnn_maxpool: bad argument");
-        return FR_ERR_ARG;
-    }
-    FR_HIP_CHECK(launch_mtcnn_maxpool(x, B, H, W, C, k, stride, pool_ceil_out(H, k, stride), pool_ceil_out(W, k, stride),
-                                      y, (hipStream_t)stream));
-    return FR_OK;
-}
-
-int fr_mtcnn_dense(const float* x, int B, int K, const float* w, const float* bias, const float* slope, int N, float* y,
-                   void* stream) {
-    if (!x || !w || !y || B <= 0 || K <= 0 || N <= 0) { set_error("fr_mtcnn_dense: bad argument"); return FR_ERR_ARG; }
-    FR_HIP_CHECK(launch_mtcnn_dense(x, B, K, w, bias, slope, N, y, (hipStream_t)stream));
-    return FR_OK;
-}
-
-int fr_mtcnn_head(const float* x, int64_t M, int C, const float* w, const float* bias, int n_out, float* out,
-                  void* stream) {
-    if (!x || !w || !bias || !out || M <= 0 || C <= 0 || n_out < 2) { set_error("fr_mtcnn_head: bad argument"); return FR_ERR_ARG; }
-    FR_HIP_CHECK(launch_mtcnn_head(x, M, C, w, bias, n_out, out, (hipStream_t)stream));
     return FR_OK;
 }
 

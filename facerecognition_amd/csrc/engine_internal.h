@@ -1,9 +1,11 @@
-// What engine.cpp (blob loader, plan builders, forward, C ABI), stages.cpp (the fused-stage kinds) and convs.cpp (the
-// conv kernel kinds: selection, tuning, launch) share: the handle, the plan's records and a few helpers.  Nothing
-// here is part of the library's ABI.
+// What engine.cpp (handle, reserve, forward, the handle's C ABI), plan.cpp (blob parser, plan builders), stages.cpp (the
+// fused-stage kinds), convs.cpp (the conv kernel kinds: selection, tuning, launch) and gallery_api.cpp (gallery and
+// matcher C ABI) share: the handle, the plan's records and a few helpers.  ops_api.cpp and the other *_api.cpp files hold
+// the handle-free C ABI groups.  Nothing here is part of the library's ABI.
 #pragma once
 #include <mutex>
 #include <string>
+#include <unordered_map>
 #include <vector>
 
 #include "../../include/frhip.h"
@@ -17,8 +19,6 @@ struct DevConvW {
     bf16_t* w = nullptr;
     float* bias = nullptr;
     float* slope = nullptr;
-    float* aff_s = nullptr;
-    float* aff_b = nullptr;
     float* bias9 = nullptr;  // [9][Npad] border-class bias (input BN folded into a 3x3/s1/p1 conv)
     bf16_t* wimg = nullptr;  // conv_img.hip K-step slice images (convs its kernels apply to)
     float* negf = nullptr;   // conv_img / conv_rows: [Npad] activation negative-side factor (slope / 0 / 1)
@@ -35,19 +35,19 @@ struct TensorDesc {
     int H, W, C;
     bf16_t* dev = nullptr;
     std::string name;  // oracle module whose output this tensor equals ("" = internal)
-    bool f16 = false;  // stored as f16 in a bf16 plan (IRV1's high-resolution stem, build_irv1)
+    bool f16 = false;  // stored as f16 in a bf16 plan (IRV1's f16 section, plan.cpp build_irv1)
 };
 
 enum OpKind { OP_PRE, OP_CONV, OP_MAXPOOL, OP_AVGPOOL, OP_HEAD, OP_STAGE };
+enum { ACT_NONE = 0, ACT_RELU = 1, ACT_PRELU = 2 };  // Op::act (and ConvArgs::act, fr_conv_desc::act)
 
 struct Op {
     OpKind kind;
     int in = -1, in_off = 0, cin = 0;
     int out = -1, out_off = 0;
     int res = -1, res_off = 0;
-    int out2 = -1;
     int kh = 1, kw = 1, sh = 1, sw = 1, ph = 0, pw = 0;
-    int act = 0;
+    int act = ACT_NONE;
     int wi = -1;
     int pk = 0, ps = 0, pp = 0;
     int stage = -1;  // OP_STAGE: its StageRec; OP_CONV: the stage that covers it (skipped when stages run)
@@ -296,6 +296,22 @@ struct ProfScope {
         h->prof_pending.push_back({cls, a, b, flops, bytes});
     }
 };
+
+// ------------------------------------------------------------------ plan.cpp
+struct HostT {  // one tensor of a weight blob
+    std::vector<int64_t> dims;
+    std::vector<float> v;
+};
+using Blob = std::unordered_map<std::string, HostT>;
+// Parses an FRW1 weight blob; touches no handle.
+int parse_blob(const void* blob, size_t n, Blob& out);
+// Runs the builder of h->arch on a cleared handle: its tensors, ops, conv weights and fused stages (the head's
+// weights join W under a conv's name).  Returns the builder's status; on failure the caller frees what was built.
+int build_plan(fr_handle* h, Blob& W);
+
+// ------------------------------------------------------------------ gallery_api.cpp
+// fr_match_topk under the handle's lock, which the caller holds (fr_embed_match).
+int match_locked(fr_handle* h, const float* P, int B, int k, float* scores, int32_t* idx, void* stream);
 
 // ------------------------------------------------------------------ stages.cpp
 // Runs the kind's weight packer on a record whose members are in place (Builder::close_stage).

@@ -1,4 +1,4 @@
-// Internal launcher interface between the C-ABI/graph runner (engine.cpp, stages.cpp, convs.cpp) and the
+// Internal launcher interface between the C-ABI/graph runner (engine.cpp, stages.cpp, convs.cpp, the *_api.cpp files) and the
 // HIP kernels (conv_igemm.hip, misc.hip, match.hip).  Not part of the public ABI.
 #pragma once
 #include "common.h"

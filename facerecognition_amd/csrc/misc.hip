@@ -16,7 +16,7 @@ namespace fr {
 namespace {
 
 // x = (u/255 - 0.5)/0.5 = (2u - 255)/255: store q = 2u - 255 (an integer in [-255, 255], exact
-// in bf16 and f16) twice; the stem weights carry 1/255 as a hi/lo pair (engine.cpp make_convw).
+// in bf16 and f16) twice; the stem weights carry 1/255 as a hi/lo pair (plan.cpp make_convw).
 template <bool F16>
 __global__ __launch_bounds__(256) void preprocess_u8_kernel(const uint8_t* __restrict__ in, int npix,
                                                             bf16_t* __restrict__ out) {

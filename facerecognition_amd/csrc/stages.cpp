@@ -1,6 +1,6 @@
 // frhip fused stages: one launch that replaces a run of member ops of a forward plan and is measured against them
 // per batch size.  This file holds what the engine knows about each kind (StageKind): the table of its fixed
-// facts, its weight packer, its launch, and the rules for when it runs.  The arch builders (engine.cpp) emit the
+// facts, its weight packer, its launch, and the rules for when it runs.  The arch builders (plan.cpp) emit the
 // stage ops and their members; DESIGN.md "Fused stage kinds" lists the steps to add a kind.
 #include <algorithm>
 #include <cstdio>
@@ -118,7 +118,7 @@ static int build_stage(fr_handle* h, StageRec& r) {
             return FR_ERR_ARG;
         }
         // the stage kernel's epilogues are specialised: conv1 = bias + PReLU, conv2 = bias + identity
-        if ((c % 2 == 0 && (op.act != 2 || !cw.slope)) || (c % 2 == 1 && (op.act != 0 || op.res < 0))) {
+        if ((c % 2 == 0 && (op.act != ACT_PRELU || !cw.slope)) || (c % 2 == 1 && (op.act != ACT_NONE || op.res < 0))) {
             set_error("plan: stage member conv has an unexpected activation / residual");
             return FR_ERR_ARG;
         }
@@ -153,10 +153,10 @@ static int build_stage(fr_handle* h, StageRec& r) {
         }
         // negative-side factor of the activation: PReLU slope, 0 for ReLU, 1 for none
         float* f = sl.data() + (size_t)c * C;
-        if (op.act == 2 && cw.slope)
+        if (op.act == ACT_PRELU && cw.slope)
             FR_HIP_CHECK(hipMemcpy(f, cw.slope, C * sizeof(float), hipMemcpyDeviceToHost));
         else
-            std::fill(f, f + C, op.act == 1 ? 0.f : 1.f);
+            std::fill(f, f + C, op.act == ACT_RELU ? 0.f : 1.f);
     }
     if (ntail) {  // rows [C half, C half + C) of the tail conv (3x3 C -> 2C): bias9 halves, PReLU slopes
         const Op& op = h->ops[r.tail_op];
@@ -266,7 +266,7 @@ static int chain_member(fr_handle* h, const StageRec& r, int per, int blk, int k
     }
     m.op = &h->ops[r.conv_ops[per * blk + k]];
     if (m.op->kind == OP_CONV) m.cw = &h->convw[m.op->wi];
-    if (m.op->kind != OP_CONV || m.cw->w8 || !m.cw->bias || m.cw->bias9 || m.op->act != 1) {
+    if (m.op->kind != OP_CONV || m.cw->w8 || !m.cw->bias || m.cw->bias9 || m.op->act != ACT_RELU) {
         set_error("plan: " + name + " member conv is not bf16 / f16 + bias + ReLU");
         return FR_ERR_ARG;
     }
@@ -324,6 +324,7 @@ static int build_chain17(fr_handle* h, StageRec& r) {
 
 // Packs ResNet-50 layer3.1 .. layer3.5's member convs (per block: conv1 1x1 1024 -> 256, conv2 3x3 256 -> 256,
 // conv3 1x1 256 -> 1024 with the residual; BN folded, each + bias + ReLU) into conv_chain_r50.hip's per-wave streams.
+// Members without the kernel's shapes fail the load (no fall-back to the member ops).
 static int build_chain_r50(fr_handle* h, StageRec& r) {
     const int nblk = r.nblk;
     std::vector<bf16_t> packed(chain_r50_weight_elems(nblk));
@@ -355,6 +356,7 @@ static int build_chain_r50(fr_handle* h, StageRec& r) {
 
 // Packs ResNet-50 layer1.1 / layer1.2's member convs (conv1 1x1 256 -> 64, conv2 3x3 64 -> 64, conv3 1x1 64 -> 256
 // with the residual; BN folded, each + bias + ReLU) into conv_bneck28.hip's per-quarter register images.
+// Members without the kernel's shapes fail the load (no fall-back to the member ops).
 static int build_bneck28(fr_handle* h, StageRec& r) {
     const int nblk = r.nblk;
     if ((int)r.x_tensors.size() != nblk) return bad_shapes("bneck28 member count");

@@ -13,7 +13,7 @@
   crops (``facerecognition_amd/synth/<arch>_bnstats.npz``, written by tools/calibrate_bn.py);
   SURVEY.md §0.5 explains why uncalibrated random BN stats collapse the embeddings.
 * ``fold_state_dict`` folds every eval-mode BatchNorm into the adjacent conv/linear (in f64)
-  and emits the tensor names the native plans in csrc/engine.cpp expect.
+  and emits the tensor names the native plans in csrc/plan.cpp expect.
 * ``load_checkpoint`` reads the reference's training checkpoint schema
   (``model_state_dict``/``config``/``num_classes``; models/arcface/train_arcface.py:755-772)
   with ``torch.load(weights_only=True)`` — never an unpickling loader.
@@ -270,7 +270,7 @@ def _fold_pre_bn_3x3(out: dict, name: str, w: np.ndarray, s1, t1, s2, t2, slope)
 
 
 def fold_state_dict(arch: str, sd) -> Dict[str, np.ndarray]:
-    """Eval-mode BN folding (f64) → the tensor names of csrc/engine.cpp's plans."""
+    """Eval-mode BN folding (f64) → the tensor names of csrc/plan.cpp's plans."""
     eps = BN_EPS[arch]
     out: Dict[str, np.ndarray] = {}
     if arch == "resnet50_arcface":

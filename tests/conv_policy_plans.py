@@ -9,7 +9,11 @@ writes those files (they are recorded at the commit before a change to the conv 
 
 One file per model: {"B=<batch> invariant=<0|1>": [plan lines]}.  B = 1 and 8 reach fit_split's small-M splits, B = 256
 the ROWS / IMG28 / BAND ranks of the policy, invariant = 1 the unsplit cost-model branch (refused on fp8 handles, so
-those have the invariant = 0 plans only)."""
+those have the invariant = 0 plans only).
+
+fr_debug_plan does not show the plan's tensors, so a second file per model, <name>_tensors.json, pins them:
+{"tensors": [[name, H, W, C, dtype]]} in plan order, dtype the storage type ("bf16", "f16") that fr_debug_tensor_dtype
+reports (a bf16 InceptionResnetV1 plan keeps a section in f16)."""
 from __future__ import annotations
 
 import ctypes
@@ -52,6 +56,24 @@ def plans(name):
     return out
 
 
+def tensors(name):
+    from facerecognition_amd.model import FRModel
+    arch, dtype = MODELS[name]
+    m = FRModel.synthetic(arch, dtype=dtype)
+    L = N.lib()
+    dtypes = {v: k for k, v in N.FR_DTYPE.items()}
+    out = []
+    try:
+        for t in range(L.fr_debug_tensor_count(m.handle)):
+            H, W, C = ctypes.c_int(), ctypes.c_int(), ctypes.c_int()
+            N.check(L.fr_debug_tensor_shape(m.handle, t, ctypes.byref(H), ctypes.byref(W), ctypes.byref(C)))
+            out.append([L.fr_debug_tensor_name(m.handle, t).decode(), H.value, W.value, C.value,
+                        dtypes[L.fr_debug_tensor_dtype(m.handle, t)]])
+    finally:
+        m.close()
+    return {"tensors": out}
+
+
 def golden(name):
     with open(os.path.join(GOLDEN_DIR, name + ".json")) as f:
         return json.load(f)
@@ -63,5 +85,8 @@ if __name__ == "__main__":
     for name in MODELS:
         with open(os.path.join(out_dir, name + ".json"), "w") as f:
             json.dump(plans(name), f, indent=0, sort_keys=True)
+            f.write("\n")
+        with open(os.path.join(out_dir, name + "_tensors.json"), "w") as f:
+            json.dump(tensors(name), f, indent=0, sort_keys=True)
             f.write("\n")
         print("wrote", name)
