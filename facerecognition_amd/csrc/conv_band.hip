@@ -15,6 +15,7 @@
 // so each lane ends with 4 consecutive channels of one pixel and the fused epilogue (bias, residual,
 // ReLU/PReLU, second affine output) stores 8-byte groups straight from registers.
 // LDS rows are 128 B (64 channels); chunk index XOR (row>>1)&7, applied to the per-lane DMA source.
+#include "conv_epilogue.h"
 #include "kernels.h"
 #include "lds_dma.h"
 
@@ -31,7 +32,7 @@ constexpr int MAXPW = 8;  // max patch DMA instructions per wave per chunk
 // ReLU/PReLU, bf16/f16 store, optional second affine output.  Channel-outer so the per-channel vectors
 // load once per fragment column; residual loads are unconditional (invalid lanes read pixel 0) so the
 // FM loads of a column are in flight together; only the stores are predicated.
-template <class T, int W, int Wp, int Mv, int FM, int FN>
+template <bool F16, int W, int Wp, int Mv, int FM, int FN>
 __device__ __forceinline__ void band_epilogue(const ConvArgs& p, const f32x4_t (&acc)[FN][FM], int lane, int wm,
                                               int wn, size_t pix0, int n0) {
     int pix_off[FM];
@@ -48,10 +49,8 @@ __device__ __forceinline__ void band_epilogue(const ConvArgs& p, const f32x4_t (
         const int n_raw = n0 + wn * 16 * FN + 16 * i + 4 * (lane >> 4);
         const bool nv = n_raw < p.Cout;
         const int n = nv ? n_raw : 0;
-        float4 bb = make_float4(0.f, 0.f, 0.f, 0.f), sl = bb, as = bb, ab = bb;
-        if (p.bias && !p.bias9) bb = *(const float4*)(p.bias + n);
-        if (p.act == 2) sl = *(const float4*)(p.slope + n);
-        if (p.y2) { as = *(const float4*)(p.aff_s + n); ab = *(const float4*)(p.aff_b + n); }
+        ConvEpilogue<F16, 4, EPI_Y2 | EPI_BIAS9> ep;
+        ep.load(p, n);
         uint2 rr[FM];
         if (p.res) {
 #pragma unroll
@@ -60,38 +59,10 @@ __device__ __forceinline__ void band_epilogue(const ConvArgs& p, const f32x4_t (
         }
 #pragma unroll
         for (int j = 0; j < FM; ++j) {
-            float v[4] = {acc[i][j][0] + bb.x, acc[i][j][1] + bb.y, acc[i][j][2] + bb.z, acc[i][j][3] + bb.w};
-            if (p.bias9) {
-                const int po = pix_off[j], oh = (int)((pix0 / W) % p.Ho) + po / W;
-                const float4 b9 = *(const float4*)(p.bias9 + (size_t)border_class(oh, po % W, p.Ho, W) * p.Npad + n);
-                v[0] += b9.x; v[1] += b9.y; v[2] += b9.z; v[3] += b9.w;
-            }
-            if (p.res) {
-                float f[8];
-                T::unpack8(make_uint4(rr[j].x, rr[j].y, 0, 0), f);
-                v[0] += f[0]; v[1] += f[1]; v[2] += f[2]; v[3] += f[3];
-            }
-            if (p.act == 1) {
-#pragma unroll
-                for (int e = 0; e < 4; ++e) v[e] = v[e] > 0.f ? v[e] : 0.f;
-            } else if (p.act == 2) {
-                v[0] = v[0] > 0.f ? v[0] : v[0] * sl.x;
-                v[1] = v[1] > 0.f ? v[1] : v[1] * sl.y;
-                v[2] = v[2] > 0.f ? v[2] : v[2] * sl.z;
-                v[3] = v[3] > 0.f ? v[3] : v[3] * sl.w;
-            }
-            if (pv[j] && nv) {
-                const size_t pix = pix0 + pix_off[j];
-                float o8[8] = {v[0], v[1], v[2], v[3], 0, 0, 0, 0};
-                const uint4 pk = T::pack8(o8);
-                *(uint2*)(p.y + pix * p.Cy + p.y_off + n) = make_uint2(pk.x, pk.y);
-                if (p.y2) {
-                    float u8[8] = {v[0] * as.x + ab.x, v[1] * as.y + ab.y, v[2] * as.z + ab.z, v[3] * as.w + ab.w,
-                                   0, 0, 0, 0};
-                    const uint4 pk2 = T::pack8(u8);
-                    *(uint2*)(p.y2 + pix * p.Cy2 + p.y2_off + n) = make_uint2(pk2.x, pk2.y);
-                }
-            }
+            float v[4] = {acc[i][j][0], acc[i][j][1], acc[i][j][2], acc[i][j][3]};
+            const int po = pix_off[j], oh = (int)((pix0 / W) % p.Ho) + po / W;
+            ep.apply(p, v, p.res != nullptr, rr[j], border_class(oh, po % W, p.Ho, W));
+            if (pv[j] && nv) ep.store(p, pix0 + pix_off[j], n, v);
         }
     }
 }
@@ -101,7 +72,7 @@ __device__ __forceinline__ void band_epilogue(const ConvArgs& p, const f32x4_t (
 // conflicts), then all threads emit coalesced 8-channel groups: 16-B loads of the residual (issued
 // before the LDS round trip), 16-B stores of y / y2, per-channel vectors loaded once per pass (a
 // thread's channel group is fixed).  Row groups (MP > 1) keep the staged rows within the LDS.
-template <class T, int W, int Wp, int Mv, int FM, int FN, int WM, int WN>
+template <bool F16, int W, int Wp, int Mv, int FM, int FN, int WM, int WN>
 __device__ __forceinline__ void band_epilogue_lds(const ConvArgs& p, const f32x4_t (&acc)[FN][FM], char* smem,
                                                   int tid, int lane, int wm, int wn, size_t pix0, int n0) {
     constexpr int NT = 64 * WM * WN;
@@ -135,21 +106,8 @@ __device__ __forceinline__ void band_epilogue_lds(const ConvArgs& p, const f32x4
             pixo[it] = ok[it] ? r * W + c : 0;
             if (p.res) rr[it] = *(const uint4*)(p.res + (pix0 + pixo[it]) * p.Cres + p.res_off + nn);
         }
-        float b8[8] = {0, 0, 0, 0, 0, 0, 0, 0}, s8[8], as8[8], ab8[8];
-        if (p.bias && !p.bias9) {
-            const float4 x0 = *(const float4*)(p.bias + nn), x1 = *(const float4*)(p.bias + nn + 4);
-            b8[0] = x0.x; b8[1] = x0.y; b8[2] = x0.z; b8[3] = x0.w; b8[4] = x1.x; b8[5] = x1.y; b8[6] = x1.z; b8[7] = x1.w;
-        }
-        if (p.act == 2) {
-            const float4 x0 = *(const float4*)(p.slope + nn), x1 = *(const float4*)(p.slope + nn + 4);
-            s8[0] = x0.x; s8[1] = x0.y; s8[2] = x0.z; s8[3] = x0.w; s8[4] = x1.x; s8[5] = x1.y; s8[6] = x1.z; s8[7] = x1.w;
-        }
-        if (p.y2) {
-            const float4 x0 = *(const float4*)(p.aff_s + nn), x1 = *(const float4*)(p.aff_s + nn + 4);
-            const float4 y0 = *(const float4*)(p.aff_b + nn), y1 = *(const float4*)(p.aff_b + nn + 4);
-            as8[0] = x0.x; as8[1] = x0.y; as8[2] = x0.z; as8[3] = x0.w; as8[4] = x1.x; as8[5] = x1.y; as8[6] = x1.z; as8[7] = x1.w;
-            ab8[0] = y0.x; ab8[1] = y0.y; ab8[2] = y0.z; ab8[3] = y0.w; ab8[4] = y1.x; ab8[5] = y1.y; ab8[6] = y1.z; ab8[7] = y1.w;
-        }
+        ConvEpilogue<F16, 8, EPI_Y2 | EPI_BIAS9> ep;
+        ep.load(p, nn);
         if (wn == pn && wm / (WM / MP) == mp) {
 #pragma unroll
             for (int i = 0; i < FN; ++i)
@@ -164,40 +122,11 @@ __device__ __forceinline__ void band_epilogue_lds(const ConvArgs& p, const f32x4
         for (int it = 0; it < IT; ++it) {
             const int ml = r0 + it * RS;
             if (ml < GR) {
-                const float4 v0 = *(const float4*)(smem + ml * LD + g * 32);
-                const float4 v1 = *(const float4*)(smem + ml * LD + g * 32 + 16);
-                float v[8] = {v0.x + b8[0], v0.y + b8[1], v0.z + b8[2], v0.w + b8[3],
-                              v1.x + b8[4], v1.y + b8[5], v1.z + b8[6], v1.w + b8[7]};
-                if (p.bias9) {
-                    const int po = pixo[it], oh = (int)((pix0 / W) % p.Ho) + po / W;
-                    const float* bb = p.bias9 + (size_t)border_class(oh, po % W, p.Ho, W) * p.Npad + nn;
-                    const float4 x0 = *(const float4*)bb, x1 = *(const float4*)(bb + 4);
-                    v[0] += x0.x; v[1] += x0.y; v[2] += x0.z; v[3] += x0.w;
-                    v[4] += x1.x; v[5] += x1.y; v[6] += x1.z; v[7] += x1.w;
-                }
-                if (p.res) {
-                    float f[8];
-                    T::unpack8(rr[it], f);
-#pragma unroll
-                    for (int e = 0; e < 8; ++e) v[e] += f[e];
-                }
-                if (p.act == 1) {
-#pragma unroll
-                    for (int e = 0; e < 8; ++e) v[e] = v[e] > 0.f ? v[e] : 0.f;
-                } else if (p.act == 2) {
-#pragma unroll
-                    for (int e = 0; e < 8; ++e) v[e] = v[e] > 0.f ? v[e] : v[e] * s8[e];
-                }
-                if (ok[it]) {
-                    const size_t pix = pix0 + pixo[it];
-                    *(uint4*)(p.y + pix * p.Cy + p.y_off + n) = T::pack8(v);
-                    if (p.y2) {
-                        float u[8];
-#pragma unroll
-                        for (int e = 0; e < 8; ++e) u[e] = v[e] * as8[e] + ab8[e];
-                        *(uint4*)(p.y2 + pix * p.Cy2 + p.y2_off + n) = T::pack8(u);
-                    }
-                }
+                float v[8];
+                load_f((const float*)(smem + ml * LD + g * 32), v);
+                const int po = pixo[it], oh = (int)((pix0 / W) % p.Ho) + po / W;
+                ep.apply(p, v, p.res != nullptr, rr[it], border_class(oh, po % W, p.Ho, W));
+                if (ok[it]) ep.store(p, pix0 + pixo[it], n, v);
             }
         }
         __syncthreads();
@@ -378,7 +307,7 @@ __global__ __launch_bounds__(64 * WM * WN, 1) void conv3x3_band_kernel(ConvArgs 
         }
     }
 
-    band_epilogue<T, W, Wp, Mv, FM, FN>(p, acc, lane, wm, wn, (size_t)(b * H + oh0) * W, n0);
+    band_epilogue<F16, W, Wp, Mv, FM, FN>(p, acc, lane, wm, wn, (size_t)(b * H + oh0) * W, n0);
 }
 
 // Software-pipelined band kernel: one wave per SIMD (4 waves, 512-register budget), each wave owning
@@ -606,7 +535,7 @@ __global__ __launch_bounds__(64 * WM * WN, 1) void conv3x3_bandp_kernel(ConvArgs
     wait_vm<0>();  // the tail re-fetches must land before the workgroup's LDS is released
 
     __syncthreads();  // every wave is past its last LDS read before the staging overwrites the ring
-    band_epilogue_lds<T, W, Wp, Mv, FM, FN, WM, WN>(p, acc, smem, threadIdx.x, lane, wm, wn,
+    band_epilogue_lds<F16, W, Wp, Mv, FM, FN, WM, WN>(p, acc, smem, threadIdx.x, lane, wm, wn,
                                                      (size_t)(b * H + oh0) * W, n0);
 }
 

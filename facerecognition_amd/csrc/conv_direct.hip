@@ -18,7 +18,7 @@
 //   * patch positions are CINB + 32 bytes apart when CINB / 16 is even (CINB = 2 Cin): 16 consecutive
 //     positions x 4 lane groups then hit 16 distinct 16-B bank groups (conflict-free ds_read_b128);
 //   * the K order (32-deep MFMA chunks of the flattened K) and the epilogue arithmetic (bias, then the
-//     activation, as conv_igemm's epilogue8) are the implicit GEMM's, so the output equals conv_igemm
+//     activation: conv_epilogue.h's, in this file's own copy) are the implicit GEMM's, so the output equals conv_igemm
 //     tile 0 bit for bit and the per-shape autotuner can time this kernel beside the igemm tiles.
 #include "kernels.h"
 #include "lds_dma.h"
@@ -175,7 +175,7 @@ __global__ __launch_bounds__(64 * DNW, OCC) void conv_direct_kernel(ConvArgs p, 
                     for (int j = 0; j < FW; ++j) acc[i][j] = T::mfma(wa[ks][i], fb[ks & 1][j], acc[i][j]);
             }
         }
-        // ---- epilogue (conv_igemm epilogue8's arithmetic): bias, activation, pack, 8-B buffer stores
+        // ---- epilogue (conv_epilogue.h's arithmetic, own copy: DESIGN.md): bias, activation, pack, 8-B buffer stores
         // (pixels past the unit: out-of-range offsets, so every wave issues exactly NF * FW stores)
 #pragma unroll
         for (int i = 0; i < NF; ++i) {
@@ -206,11 +206,8 @@ __global__ __launch_bounds__(64 * DNW, OCC) void conv_direct_kernel(ConvArgs p, 
         }
         // the next unit's rows landed (they precede this unit's NF * FW stores, which stay in flight) and
         // every wave is past its reads of `buf`, which the next iteration's DMA overwrites
-        if constexpr (NF * FW == 32) asm volatile("s_waitcnt vmcnt(32)" ::: "memory");
-        else if constexpr (NF * FW == 16) asm volatile("s_waitcnt vmcnt(16)" ::: "memory");
-        else if constexpr (NF * FW == 8) asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
-        else if constexpr (NF * FW == 4) asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
-        else asm volatile("s_waitcnt vmcnt(2)" ::: "memory");
+        static_assert(NF * FW >= 2 && NF * FW <= 32, "counted wait for this unit's stores");
+        wait_vm<NF * FW>();
         asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
         cur = nxt;
         buf ^= 1;
@@ -220,7 +217,7 @@ __global__ __launch_bounds__(64 * DNW, OCC) void conv_direct_kernel(ConvArgs p, 
 // 1x1 / stride-1 / unpadded convs: a unit's pixels are contiguous NHWC rows, so operand B goes straight
 // from global memory into registers (no patch, no LDS): every K-step's fragment of the unit at once,
 // the next unit's during this unit's MFMAs (two register sets).  Units run over all B * H * W pixels.
-// Epilogue as conv_igemm's epilogue8: bias, residual, activation.
+// Epilogue as conv_epilogue.h's (own copy): bias, residual, activation.
 template <bool F16, int NF, int FW, int KSR>  // KSR: K-steps compiled (>= Kpad / 32; the rest read zeros)
 __global__ __launch_bounds__(64 * DNW, 1) void conv_direct1_kernel(ConvArgs p, DGeo g) {
     typedef Num<F16> T;

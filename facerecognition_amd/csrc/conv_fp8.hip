@@ -11,6 +11,7 @@
 //     per-tensor scaling; the hardware converter does not saturate: > ~464 would become NaN).
 // The epilogue optionally records amax(|y|) of what it stores (atomicMax on the f32 bit pattern) for
 // the next conv.  Requirements: Cin % 64 == 0 (every IResNet100 conv but the bf16 stem).
+#include "conv_epilogue.h"
 #include "kernels.h"
 #include "lds_dma.h"
 
@@ -44,10 +45,6 @@ __device__ __forceinline__ uint2 cvt8(const uint4& v, float scale) {
     o1 = __builtin_amdgcn_cvt_scalef32_pk_fp8_bf16(o1, __builtin_bit_cast(bf16x2_t, v.z), scale, false);
     o1 = __builtin_amdgcn_cvt_scalef32_pk_fp8_bf16(o1, __builtin_bit_cast(bf16x2_t, v.w), scale, true);
     return make_uint2(__builtin_bit_cast(uint32_t, o0), __builtin_bit_cast(uint32_t, o1));
-}
-
-__device__ __forceinline__ void atomic_amax(float* dst, float v) {
-    atomicMax((unsigned int*)dst, __float_as_uint(v));  // v >= 0: the f32 bit order is the value order
 }
 
 // blocks per CU that the two LDS stages allow (2 x (2*BM + BN) x 128 B)
@@ -198,68 +195,22 @@ __global__ __launch_bounds__(64 * WM * WN, (Fp8Occ<BM, BN>::value)) void conv_fp
     const int n = n0 + gg * 8;
     const bool nv = n < p.Cout;
     const int nn = nv ? n : 0;
-    float ws8[8], b8[8] = {0, 0, 0, 0, 0, 0, 0, 0}, sl8[8], as8[8], ab8[8];
-    {
-        const float4 w0 = *(const float4*)(p.wscale + nn), w1 = *(const float4*)(p.wscale + nn + 4);
-        ws8[0] = w0.x; ws8[1] = w0.y; ws8[2] = w0.z; ws8[3] = w0.w; ws8[4] = w1.x; ws8[5] = w1.y; ws8[6] = w1.z; ws8[7] = w1.w;
-    }
-    if (p.bias && !p.bias9) {
-        const float4 c0 = *(const float4*)(p.bias + nn), c1 = *(const float4*)(p.bias + nn + 4);
-        b8[0] = c0.x; b8[1] = c0.y; b8[2] = c0.z; b8[3] = c0.w; b8[4] = c1.x; b8[5] = c1.y; b8[6] = c1.z; b8[7] = c1.w;
-    }
-    if (p.act == 2) {
-        const float4 s0 = *(const float4*)(p.slope + nn), s1 = *(const float4*)(p.slope + nn + 4);
-        sl8[0] = s0.x; sl8[1] = s0.y; sl8[2] = s0.z; sl8[3] = s0.w; sl8[4] = s1.x; sl8[5] = s1.y; sl8[6] = s1.z; sl8[7] = s1.w;
-    }
-    if (p.y2) {
-        const float4 a0 = *(const float4*)(p.aff_s + nn), a1 = *(const float4*)(p.aff_s + nn + 4);
-        const float4 c0 = *(const float4*)(p.aff_b + nn), c1 = *(const float4*)(p.aff_b + nn + 4);
-        as8[0] = a0.x; as8[1] = a0.y; as8[2] = a0.z; as8[3] = a0.w; as8[4] = a1.x; as8[5] = a1.y; as8[6] = a1.z; as8[7] = a1.w;
-        ab8[0] = c0.x; ab8[1] = c0.y; ab8[2] = c0.z; ab8[3] = c0.w; ab8[4] = c1.x; ab8[5] = c1.y; ab8[6] = c1.z; ab8[7] = c1.w;
-    }
+    ConvEpilogue<false, 8, EPI_Y2 | EPI_WSCALE | EPI_BIAS9> ep;
+    ep.load(p, nn);
     float amax = 0.f;
 #pragma unroll
     for (int it = 0; it < ITER; ++it) {
         const int ml = ml0 + it * RS, m = m0 + ml;
         if (m >= p.M || !nv) continue;
-        const float4 v0 = *(const float4*)(sE + ml * EPI_LD + gg * 8);
-        const float4 v1 = *(const float4*)(sE + ml * EPI_LD + gg * 8 + 4);
-        float v[8] = {v0.x * ws8[0] + b8[0], v0.y * ws8[1] + b8[1], v0.z * ws8[2] + b8[2], v0.w * ws8[3] + b8[3],
-                      v1.x * ws8[4] + b8[4], v1.y * ws8[5] + b8[5], v1.z * ws8[6] + b8[6], v1.w * ws8[7] + b8[7]};
-        if (p.bias9) {
-            const int r = m % HoWo;
-            const float* bb = p.bias9 + (size_t)border_class(r / p.Wo, r % p.Wo, p.Ho, p.Wo) * p.Npad + nn;
-            const float4 c0 = *(const float4*)bb, c1 = *(const float4*)(bb + 4);
-            v[0] += c0.x; v[1] += c0.y; v[2] += c0.z; v[3] += c0.w; v[4] += c1.x; v[5] += c1.y; v[6] += c1.z; v[7] += c1.w;
-        }
-        if (p.res) {
-            float f[8];
-            unpack8_bf16(*(const uint4*)(p.res + (size_t)m * p.Cres + p.res_off + n), f);
-#pragma unroll
-            for (int e = 0; e < 8; ++e) v[e] += f[e];
-        }
-        if (p.act == 1) {
-#pragma unroll
-            for (int e = 0; e < 8; ++e) v[e] = v[e] > 0.f ? v[e] : 0.f;
-        } else if (p.act == 2) {
-#pragma unroll
-            for (int e = 0; e < 8; ++e) v[e] = v[e] > 0.f ? v[e] : v[e] * sl8[e];
-        }
-#pragma unroll
-        for (int e = 0; e < 8; ++e) amax = fmaxf(amax, fabsf(v[e]));
-        *(uint4*)(p.y + (size_t)m * p.Cy + p.y_off + n) = pack8_bf16(v);
-        if (p.y2) {
-            float u[8];
-#pragma unroll
-            for (int e = 0; e < 8; ++e) u[e] = v[e] * as8[e] + ab8[e];
-            *(uint4*)(p.y2 + (size_t)m * p.Cy2 + p.y2_off + n) = pack8_bf16(u);
-        }
+        float v[8];
+        load_f(sE + ml * EPI_LD + gg * 8, v);
+        uint4 r;
+        if (p.res) r = *(const uint4*)(p.res + (size_t)m * p.Cres + p.res_off + n);
+        ep.apply(p, v, p.res != nullptr, r, border_class_of(p, m));
+        amax = amax_fold(amax, v);
+        ep.store(p, m, n, v);
     }
-    if (p.y_amax) {
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) amax = fmaxf(amax, __shfl_xor(amax, o));
-        if (lane == 0) atomic_amax(p.y_amax + blockIdx.x % max(p.amax_slots, 1), amax);
-    }
+    if (p.y_amax) amax_publish(p.y_amax, blockIdx.x % max(p.amax_slots, 1), amax);
 }
 
 template <int BM, int BN, int WM, int WN>

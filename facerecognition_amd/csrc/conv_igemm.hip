@@ -18,6 +18,7 @@
 // (row>>1)&7 by permuting the per-lane SOURCE chunk (the DMA destination is lane-linear), which
 // makes the MFMA-fragment ds_read_b128 loads bank-conflict free.
 // FASTK (Cin % 64 == 0): a K-step is one (r, s) tap and 64 channels, tracked in scalars.
+#include "conv_epilogue.h"
 #include "kernels.h"
 #include "lds_dma.h"
 
@@ -33,7 +34,9 @@ namespace {
 
 constexpr int BK = 64;
 
-// Shared fused epilogue for 8 consecutive channels n..n+7 of output pixel m.
+// The split-K reducers' epilogue for 8 consecutive channels n..n+7 of output pixel m: conv_epilogue.h's arithmetic in
+// the reducers' own copy, each vector loaded where it is used (taken from the header it cost the conv
+// kernel, which inlines the in-launch reducer, up to 26 VGPRs and 8 spilled SGPRs).
 template <bool F16>
 __device__ __forceinline__ void epilogue8(const ConvArgs& p, float* v, int m, int n) {
     typedef Num<F16> T;
@@ -263,23 +266,8 @@ void conv_igemm_kernel(ConvArgs p, int tiles_n, int kt_per_split) {
     // Epilogue mapping (fixed 8-channel group per thread).  The per-channel vectors load now and the
     // residual tile during the last two K-steps, so the epilogue does not wait on them.
     const int nn = nv ? n : 0;
-    float bias8[8] = {0, 0, 0, 0, 0, 0, 0, 0}, sl8[8], as8[8], ab8[8];
-    if (p.bias && !p.bias9) {
-        const float4 b0 = *(const float4*)(p.bias + nn), b1 = *(const float4*)(p.bias + nn + 4);
-        bias8[0] = b0.x; bias8[1] = b0.y; bias8[2] = b0.z; bias8[3] = b0.w;
-        bias8[4] = b1.x; bias8[5] = b1.y; bias8[6] = b1.z; bias8[7] = b1.w;
-    }
-    if (p.act == 2) {
-        const float4 s0 = *(const float4*)(p.slope + nn), s1 = *(const float4*)(p.slope + nn + 4);
-        sl8[0] = s0.x; sl8[1] = s0.y; sl8[2] = s0.z; sl8[3] = s0.w;
-        sl8[4] = s1.x; sl8[5] = s1.y; sl8[6] = s1.z; sl8[7] = s1.w;
-    }
-    if (p.y2) {
-        const float4 a0 = *(const float4*)(p.aff_s + nn), a1 = *(const float4*)(p.aff_s + nn + 4);
-        const float4 c0 = *(const float4*)(p.aff_b + nn), c1 = *(const float4*)(p.aff_b + nn + 4);
-        as8[0] = a0.x; as8[1] = a0.y; as8[2] = a0.z; as8[3] = a0.w; as8[4] = a1.x; as8[5] = a1.y; as8[6] = a1.z; as8[7] = a1.w;
-        ab8[0] = c0.x; ab8[1] = c0.y; ab8[2] = c0.z; ab8[3] = c0.w; ab8[4] = c1.x; ab8[5] = c1.y; ab8[6] = c1.z; ab8[7] = c1.w;
-    }
+    ConvEpilogue<F16, 8, EPI_Y2 | EPI_YBF16 | EPI_BIAS9> ep;
+    ep.load(p, nn);
     uint4 rr[ITER];
     const bool want_res = p.res && !p.partial;
     const bool pre_res = want_res;  // the residual rides behind the last K-steps' DMA
@@ -321,13 +309,7 @@ void conv_igemm_kernel(ConvArgs p, int tiles_n, int kt_per_split) {
         for (int kt = kt0; kt < kt1; ++kt) {
             if (kt + 1 < kt1) {
                 static_assert(GROUP >= 2 && GROUP <= 9 && GROUP != 7, "counted wait for this DMA group size");
-                if constexpr (GROUP == 2) asm volatile("s_waitcnt vmcnt(2)" ::: "memory");
-                else if constexpr (GROUP == 3) asm volatile("s_waitcnt vmcnt(3)" ::: "memory");
-                else if constexpr (GROUP == 4) asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
-                else if constexpr (GROUP == 5) asm volatile("s_waitcnt vmcnt(5)" ::: "memory");
-                else if constexpr (GROUP == 6) asm volatile("s_waitcnt vmcnt(6)" ::: "memory");
-                else if constexpr (GROUP == 8) asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
-                else asm volatile("s_waitcnt vmcnt(9)" ::: "memory");
+                wait_vm<GROUP>();
             } else {
                 asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
             }
@@ -407,15 +389,9 @@ void conv_igemm_kernel(ConvArgs p, int tiles_n, int kt_per_split) {
                 v[4] += b.x; v[5] += b.y; v[6] += b.z; v[7] += b.w;
             }
             epilogue8<F16>(p, v, m, n);
-#pragma unroll
-            for (int e = 0; e < 8; ++e) amax = fmaxf(amax, fabsf(v[e]));
+            amax = amax_fold(amax, v);
         }
-        if (p.y_amax) {
-#pragma unroll
-            for (int o = 32; o > 0; o >>= 1) amax = fmaxf(amax, __shfl_xor(amax, o));
-            if ((tid & 63) == 0)
-                atomicMax((unsigned int*)p.y_amax + blockIdx.x % max(p.amax_slots, 1), __float_as_uint(amax));
-        }
+        if (p.y_amax) amax_publish(p.y_amax, blockIdx.x % max(p.amax_slots, 1), amax);
         return;
     }
     float amax = 0.f;  // max |y| of this thread's stores (fp8 consumers' dynamic activation scale)
@@ -424,9 +400,11 @@ void conv_igemm_kernel(ConvArgs p, int tiles_n, int kt_per_split) {
         const int ml = ml0 + it * RS, m = m0 + ml;
         const float4 v0 = *(const float4*)(sE + ml * EPI_LD + g * 8);
         const float4 v1 = *(const float4*)(sE + ml * EPI_LD + g * 8 + 4);
-        float v[8] = {v0.x + bias8[0], v0.y + bias8[1], v0.z + bias8[2], v0.w + bias8[3],
-                      v1.x + bias8[4], v1.y + bias8[5], v1.z + bias8[6], v1.w + bias8[7]};
-        if (p.bias9) {  // border-class bias (bias8 is zero then)
+        // ConvEpilogue::apply's arithmetic, kept inline at this one site (through the call these kernels
+        // spilled 2-4 more SGPRs)
+        float v[8] = {v0.x + ep.bias[0], v0.y + ep.bias[1], v0.z + ep.bias[2], v0.w + ep.bias[3],
+                      v1.x + ep.bias[4], v1.y + ep.bias[5], v1.z + ep.bias[6], v1.w + ep.bias[7]};
+        if (p.bias9) {  // border-class bias (ep.bias is zero then)
             const int mm = m < p.M ? m : 0, HoWo = p.Ho * p.Wo, r = mm % HoWo;
             const float* bb = p.bias9 + (size_t)border_class(r / p.Wo, r % p.Wo, p.Ho, p.Wo) * p.Npad + nn;
             const float4 b0 = *(const float4*)bb, b1 = *(const float4*)(bb + 4);
@@ -444,27 +422,14 @@ void conv_igemm_kernel(ConvArgs p, int tiles_n, int kt_per_split) {
             for (int e = 0; e < 8; ++e) v[e] = v[e] > 0.f ? v[e] : 0.f;
         } else if (p.act == 2) {
 #pragma unroll
-            for (int e = 0; e < 8; ++e) v[e] = v[e] > 0.f ? v[e] : v[e] * sl8[e];
+            for (int e = 0; e < 8; ++e) v[e] = v[e] > 0.f ? v[e] : v[e] * ep.slope[e];
         }
         if (m < p.M && nv) {
-#pragma unroll
-            for (int e = 0; e < 8; ++e) amax = fmaxf(amax, fabsf(v[e]));
-            *(uint4*)(p.y + (size_t)m * p.Cy + p.y_off + n) = F16 && p.y_bf16 ? Num<false>::pack8(v) : T::pack8(v);
-            if (p.y2) {
-                float u[8];
-#pragma unroll
-                for (int e = 0; e < 8; ++e) u[e] = v[e] * as8[e] + ab8[e];
-                *(uint4*)(p.y2 + (size_t)m * p.Cy2 + p.y2_off + n) = T::pack8(u);
-            }
+            amax = amax_fold(amax, v);
+            ep.store(p, m, n, v);
         }
     }
-    if (p.y_amax) {
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) amax = fmaxf(amax, __shfl_xor(amax, o));
-        if ((tid & 63) == 0)
-            atomicMax((unsigned int*)p.y_amax + (blockIdx.x + gridDim.x * blockIdx.y) % max(p.amax_slots, 1),
-                      __float_as_uint(amax));
-    }
+    if (p.y_amax) amax_publish(p.y_amax, (blockIdx.x + gridDim.x * blockIdx.y) % max(p.amax_slots, 1), amax);
 }
 
 template <bool F16>
@@ -482,15 +447,9 @@ __global__ __launch_bounds__(256) void splitk_epilogue_kernel(ConvArgs p) {
             v[4] += b.x; v[5] += b.y; v[6] += b.z; v[7] += b.w;
         }
         epilogue8<F16>(p, v, m, n);
-#pragma unroll
-        for (int e = 0; e < 8; ++e) amax = fmaxf(amax, fabsf(v[e]));
+        amax = amax_fold(amax, v);
     }
-    if (p.y_amax) {
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) amax = fmaxf(amax, __shfl_xor(amax, o));
-        if ((threadIdx.x & 63) == 0)
-            atomicMax((unsigned int*)p.y_amax + blockIdx.x % max(p.amax_slots, 1), __float_as_uint(amax));
-    }
+    if (p.y_amax) amax_publish(p.y_amax, blockIdx.x % max(p.amax_slots, 1), amax);
 }
 
 template <bool F16, int BM, int BN, int WM, int WN, int STAGES>

@@ -8,7 +8,7 @@
 // memory into registers, PF steps ahead, and issues 4 v_mfma_f32_16x16x32.  A 3x3 256->256 conv of one 14x14
 // image is 13 x 4 = 52 waves, ~2-3 us.  The K-concatenated 1x1 projection (a transition block's downsample,
 // ConvArgs::x2) continues the K loop.  Per output the 32-deep MFMA chain runs over k in order and the epilogue
-// is conv_igemm's (acc + bias, + the border-class bias, + residual, activation), so the result equals
+// is the shared conv_epilogue.h (acc + bias, + the border-class bias, + residual, activation), so the result equals
 // conv_igemm tile 0 bit for bit: an autotuner candidate (FR_TILE_SMALL) that changes nothing numerically.
 // KS = 4 / 8 / 16 (the candidate's split): KS waves share one tile, each over a contiguous K chunk, and sum their
 // partials through LDS in wave order before the epilogue (deterministic, but the f32 summation order of a
@@ -20,6 +20,7 @@
 // ~150 KB each.  The narrower tiles keep PF = 8 steps of loads in flight (their ring is smaller).  KS = 1 with
 // NF = 2 / 1 (one wave per 16 px x 32 / 16 ch) is also a candidate at large M: the N = 32 / 96 convs of FaceNet's
 // Block35 at bs = 256 fill half of an implicit-GEMM tile's 64 or 128 columns.
+#include "conv_epilogue.h"
 #include "kernels.h"
 #include "lds_dma.h"
 
@@ -108,17 +109,15 @@ __global__ __launch_bounds__(KS == 1 ? 256 : 64 * KS) void conv_small_kernel(Con
     };
     // the epilogue's global operands (bias, residual), loaded before the K loop: issued after the output stores
     // they could alias, each would be a full memory round trip per fragment
-    float4 bz[NFR], b9z[NFR], sz[NFR];
+    ConvEpilogue<F16, 4, EPI_YBF16> ep[NFR];
     uint2 rz[NFR];
     const int bcls = border_class(oh, ow, p.Ho, p.Wo);
 #pragma unroll
     for (int i = 0; i < NFR; ++i) {
         const int n = n0 + 16 * i + 4 * g;
         const bool nv = n < p.Cout && (KS == 1 || i == wv);  // KS > 1: wave i runs fragment i's epilogue
-        const float4 z = make_float4(0.f, 0.f, 0.f, 0.f);
-        bz[i] = (p.bias && !p.bias9 && nv) ? *(const float4*)(p.bias + n) : z;
-        b9z[i] = (p.bias9 && nv) ? *(const float4*)(p.bias9 + (size_t)bcls * p.Npad + n) : z;
-        sz[i] = (p.act == 2 && nv) ? *(const float4*)(p.slope + n) : z;
+        ep[i].load(p, n, nv);
+        ep[i].load_bias9(p, bcls, nv);
         rz[i] = (p.res && mv && nv) ? *(const uint2*)(p.res + (size_t)m * p.Cres + p.res_off + n) : make_uint2(0u, 0u);
     }
 #pragma unroll
@@ -150,31 +149,14 @@ __global__ __launch_bounds__(KS == 1 ? 256 : 64 * KS) void conv_small_kernel(Con
             }
     }
     if (!mv) return;
-    // epilogue (conv_igemm's arithmetic): lane holds channels n .. n + 3 of fragment i of pixel m
+    // epilogue: lane holds channels n .. n + 3 of fragment i of pixel m
 #pragma unroll
     for (int i = 0; i < NFR; ++i) {
         const int n = n0 + 16 * i + 4 * g;
         if (n >= p.Cout || (KS > 1 && i != wv)) continue;
-        float v[4] = {acc[i][0] + bz[i].x, acc[i][1] + bz[i].y, acc[i][2] + bz[i].z, acc[i][3] + bz[i].w};
-        if (p.bias9) {
-            v[0] += b9z[i].x; v[1] += b9z[i].y; v[2] += b9z[i].z; v[3] += b9z[i].w;
-        }
-        if (p.res) {
-            float f[8];
-            T::unpack8(make_uint4(rz[i].x, rz[i].y, 0u, 0u), f);
-#pragma unroll
-            for (int e = 0; e < 4; ++e) v[e] += f[e];
-        }
-        if (p.act == 1) {
-#pragma unroll
-            for (int e = 0; e < 4; ++e) v[e] = v[e] > 0.f ? v[e] : 0.f;
-        } else if (p.act == 2) {
-#pragma unroll
-            for (int e = 0; e < 4; ++e) v[e] = v[e] > 0.f ? v[e] : v[e] * (&sz[i].x)[e];
-        }
-        float o8[8] = {v[0], v[1], v[2], v[3], 0.f, 0.f, 0.f, 0.f};
-        const uint4 pk = F16 && p.y_bf16 ? Num<false>::pack8(o8) : T::pack8(o8);
-        *(uint2*)(p.y + (size_t)m * p.Cy + p.y_off + n) = make_uint2(pk.x, pk.y);
+        float v[4] = {acc[i][0], acc[i][1], acc[i][2], acc[i][3]};
+        ep[i].apply(p, v, p.res != nullptr, rz[i]);
+        ep[i].store(p, m, n, v);
     }
 }
 

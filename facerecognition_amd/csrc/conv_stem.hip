@@ -122,9 +122,9 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) void s
         const uint32_t* sr = sraw + 512 * (j & 1);
         // this tile's DMA landed.  VMEM order: DMA 0, DMA 1, then per tile i: DMA i + 2 (2 ops), 7 stores;
         // younger than DMA j: DMA 1 (j = 0); DMA 2 + stores 0 (j = 1); stores j-2, DMA j+1, stores j-1
-        if (j == 0) asm volatile("s_waitcnt vmcnt(2)" ::: "memory");
-        else if (j == 1) asm volatile("s_waitcnt vmcnt(9)" ::: "memory");
-        else asm volatile("s_waitcnt vmcnt(16)" ::: "memory");
+        if (j == 0) wait_vm<2>();
+        else if (j == 1) wait_vm<9>();
+        else wait_vm<16>();
         // the previous tile's reads of sraw / sx / sy all precede a barrier every thread has passed
         lds_barrier();
         // -> 2q - 255 in the activation dtype, zero halo columns (rows outside the image were zeroed above

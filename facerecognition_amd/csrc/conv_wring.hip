@@ -20,6 +20,7 @@
 //     one barrier per stage behind a counted vmcnt wait (the younger weight loads stay in flight);
 //   * epilogue through an f32 LDS tile (bias or border-class bias, residual, ReLU/PReLU, coalesced
 //     8-channel stores), as conv_igemm.hip.
+#include "conv_epilogue.h"
 #include "kernels.h"
 #include "lds_dma.h"
 
@@ -263,46 +264,16 @@ __global__ __launch_bounds__(64 * NW, 8 / NW) void conv_wring_kernel(ConvArgs p,
         for (int j = 0; j < FM; ++j)
             *(f32x4_t*)(sE + (16 * j + (lane & 15)) * EPI_LD + 32 * wave + 16 * i + 4 * (lane >> 4)) = acc[i][j];
     __syncthreads();
-    float bias8[8] = {0, 0, 0, 0, 0, 0, 0, 0}, sl8[8];
-    if (p.bias && !p.bias9) {
-        const float4 b0 = *(const float4*)(p.bias + n), b1 = *(const float4*)(p.bias + n + 4);
-        bias8[0] = b0.x; bias8[1] = b0.y; bias8[2] = b0.z; bias8[3] = b0.w;
-        bias8[4] = b1.x; bias8[5] = b1.y; bias8[6] = b1.z; bias8[7] = b1.w;
-    }
-    if (p.act == 2) {
-        const float4 s0 = *(const float4*)(p.slope + n), s1 = *(const float4*)(p.slope + n + 4);
-        sl8[0] = s0.x; sl8[1] = s0.y; sl8[2] = s0.z; sl8[3] = s0.w;
-        sl8[4] = s1.x; sl8[5] = s1.y; sl8[6] = s1.z; sl8[7] = s1.w;
-    }
+    ConvEpilogue<F16, 8, EPI_YBF16 | EPI_BIAS9> ep;
+    ep.load(p, n);
 #pragma unroll
     for (int it = 0; it < ITER; ++it) {
         const int ml = ml0 + it * RS, m = m0 + ml;
         if (m >= p.M) continue;
-        const float4 v0 = *(const float4*)(sE + ml * EPI_LD + g * 8);
-        const float4 v1 = *(const float4*)(sE + ml * EPI_LD + g * 8 + 4);
-        float v[8] = {v0.x + bias8[0], v0.y + bias8[1], v0.z + bias8[2], v0.w + bias8[3],
-                      v1.x + bias8[4], v1.y + bias8[5], v1.z + bias8[6], v1.w + bias8[7]};
-        if (p.bias9) {  // border-class bias (bias8 is zero then)
-            const int r = m % HoWo;
-            const float* bb = p.bias9 + (size_t)border_class(r / p.Wo, r % p.Wo, p.Ho, p.Wo) * p.Npad + n;
-            const float4 b0 = *(const float4*)bb, b1 = *(const float4*)(bb + 4);
-            v[0] += b0.x; v[1] += b0.y; v[2] += b0.z; v[3] += b0.w;
-            v[4] += b1.x; v[5] += b1.y; v[6] += b1.z; v[7] += b1.w;
-        }
-        if (p.res) {
-            float f[8];
-            T::unpack8(rr[it], f);
-#pragma unroll
-            for (int e = 0; e < 8; ++e) v[e] += f[e];
-        }
-        if (p.act == 1) {
-#pragma unroll
-            for (int e = 0; e < 8; ++e) v[e] = v[e] > 0.f ? v[e] : 0.f;
-        } else if (p.act == 2) {
-#pragma unroll
-            for (int e = 0; e < 8; ++e) v[e] = v[e] > 0.f ? v[e] : v[e] * sl8[e];
-        }
-        *(uint4*)(p.y + (size_t)m * p.Cy + p.y_off + n) = F16 && p.y_bf16 ? Num<false>::pack8(v) : T::pack8(v);
+        float v[8];
+        load_f(sE + ml * EPI_LD + g * 8, v);
+        ep.apply(p, v, p.res != nullptr, rr[it], border_class_of(p, m));
+        ep.store(p, m, n, v);
     }
 }
 
